@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- TextBoost train steps/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]      N > 1: this process launches N ranks itself (torch.distributed.run on 127.0.0.1)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                                                          N > 1: this process launches N ranks itself (torch.distributed.run on 127.0.0.1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
                                                           (an existing launch: ranks from RANK / LOCAL_RANK / WORLD_SIZE; N must match)
 
@@ -344,6 +345,32 @@ def make_feeder(step, args, rank):
     return feed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_TABLE_SAMPLE_ROWS = 1024
+
+
+def dump_outputs(step, sc, out_dir):
+    """--dump-outputs: what the timed step handed its caller after the last timed step, as DIR/<name>.npy (float32 / float64) -- the step's
+    scalars, the trainable parameters it updated (LoRA factors, added token rows), the trainable gradient it computed, and a fixed sample of
+    the decayed original token rows (the whole table is 150+ MB; rows drawn by a seeded permutation, sorted).  Returns {name: shape}."""
+    import numpy as np
+    te = step.te
+    arrays = {k: np.asarray([v], dtype=np.float64) for k, v in sc.items()}
+    if te.r > 0:
+        arrays["lora_A"] = te.lora_A.detach().float().cpu().numpy()
+        arrays["lora_B"] = te.lora_B.detach().float().cpu().numpy()
+    arrays["added_embeddings"] = te.token_table[te.first_added:].detach().float().cpu().numpy()
+    rows = torch.randperm(te.first_added, generator=torch.Generator().manual_seed(0))[:DUMP_TABLE_SAMPLE_ROWS].sort().values
+    arrays["token_table_sample"] = te.token_table[rows.to(te.token_table.device)].detach().float().cpu().numpy()
+    arrays["grad"] = step.flat_grad.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def plan_launch(gpus, env, device_count):
     """What `bench.py --gpus N` does in this process (pure host logic, covered by tests/test_host_logic.py).
 
@@ -423,7 +450,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (scalars, updated trainable parameters, gradient, "
+                         "a seeded sample of the token table) as DIR/<name>.npy, float32 / float64, rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.vae = args.vae or args.feeder
     if args.precision == "fp32":
         global MFMA_PEAK_TFLOPS
@@ -497,9 +529,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     sc = step.scalars()
-    roof, table = (None, None)
+    if rank == 0 and args.dump_outputs:  # before the roofline leg: its extra eager step changes the parameters
+        dump_outputs(step, sc, args.dump_outputs)
+    roof = None
     if rank == 0 and not args.no_roofline:
-        roof, table = roofline_leg(step)
+        roof, _ = roofline_leg(step)
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not sd21 and not args.vae and args.precision == "fp16":  # the CPU baseline is the headline workload's
         try:
@@ -568,10 +602,6 @@ def main():
                 roof["frac_of_sustained_peak"] = round(roof["mfma_frac" if "mfma_frac" in roof else "frac"] * MFMA_PEAK_TFLOPS / sp, 4)
                 roof["whole_step_frac_of_sustained_peak"] = round(out["alg_tflops_per_gpu"] / sp, 4)
                 roof["dominant_tile_clock"] = dominant_tile_clock(batch=args.batch if args.batch in (1, 2, 4, 8, 16) else 8)
-        if table is not None:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_kernel_table.json"), "w") as f:
-                json.dump(table, f, indent=1)
     if dist is not None:
         dist.destroy_process_group()  # before the JSON line: RCCL prints its banner on teardown
     if rank == 0:

@@ -304,3 +304,35 @@ def test_bench_classifies_every_recorded_kernel_family():
             "layernorm_fwd": "norm", "layernorm_bwd": "norm"}
     for name, cls in want.items():
         assert b.kernel_class(name) == cls, name
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: every array the step hands back lands as DIR/<name>.npy in float32 / float64, the token-table sample is the same
+    seeded rows on every call, and the whole dump stays under 64 MB (a stand-in step on CPU tensors: no GPU here)."""
+    import types
+
+    import numpy as np
+    b = _bench()
+    V, n_added, D, L, r = 5000, 3, 16, 2, 4
+    table = torch.randn(V + n_added, D, generator=torch.Generator().manual_seed(1)).half()
+    te = types.SimpleNamespace(r=r, lora_A=torch.randn(L, 3 * r, D), lora_B=torch.randn(L, 3 * D, r), token_table=table, first_added=V)
+    step = types.SimpleNamespace(te=te, flat_grad=torch.randn(2 * L * 3 * r * D + n_added * D))
+    sc = {"loss_mse": 0.5, "loss_kpl": 0.25, "loss": 0.525, "loss_scale": 65536.0, "grad_norm": 1.5, "found_inf": 0.0, "opt_steps": 7.0}
+    shapes = b.dump_outputs(step, sc, str(tmp_path / "a"))
+    b.dump_outputs(step, sc, str(tmp_path / "b"))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(k + ".npy" for k in shapes)
+    total = 0
+    for n in names:
+        a, a2 = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, a2), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "opt_steps.npy").tolist() == [7.0]
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "added_embeddings.npy"), table[V:].float().numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "grad.npy"), step.flat_grad.numpy())
+    sample = np.load(tmp_path / "a" / "token_table_sample.npy")
+    assert sample.shape == (b.DUMP_TABLE_SAMPLE_ROWS, D)
+    rows = [int(np.flatnonzero((table[:V].float().numpy() == s).all(1))[0]) for s in sample[:8]]
+    assert rows == sorted(rows) and all(i < V for i in rows)     # original rows only, in ascending order
