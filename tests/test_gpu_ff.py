@@ -35,7 +35,7 @@ def _ref_fwd(x, w1, b1, w2, b2, R):
     return proj, y + (R.float() if R is not None else 0)
 
 
-@pytest.mark.parametrize("M,with_r", [(128, True), (384, False), (4096, True)])
+@pytest.mark.parametrize("M,with_r", [(128, True), (384, False), (4096, True), (8 * 5184, True)])   # (8 x 72x72 maps: tiles straddle images)
 def test_ff_forward_vs_torch_and_vs_the_two_launch_path(M, with_r):
     ops, L = _ops()
     assert ops.ff_fused_ok(M, C, INNER) and not ops.ff_fused_ok(M + 64, C, INNER) and not ops.ff_fused_ok(M, 640, 2560)
@@ -61,7 +61,7 @@ def test_ff_forward_vs_torch_and_vs_the_two_launch_path(M, with_r):
     assert rel_err(y, y2) < 3e-4
 
 
-@pytest.mark.parametrize("M,with_r", [(128, False), (384, True), (4096, False)])
+@pytest.mark.parametrize("M,with_r", [(128, False), (384, True), (4096, False), (8 * 5184, True)])
 def test_ff_backward_vs_autograd_and_vs_the_two_launch_path(M, with_r):
     ops, L = _ops()
     torch.manual_seed(M + 1)
@@ -95,7 +95,7 @@ def test_ff_backward_vs_autograd_and_vs_the_two_launch_path(M, with_r):
     assert rel_err(dx, dx2) < 3e-4
 
 
-@pytest.mark.parametrize("M", [256, 4096, 32768])
+@pytest.mark.parametrize("M", [256, 4096, 32768, 8 * 5184])
 def test_ff_backward_with_the_layernorm_backward_in_its_epilogue(M):
     """round 5 (tb_ff_desc.ln_x / ln_stats / ln_gamma): the fused feed-forward backward applies norm3's LayerNorm backward to its accumulators and
     adds the residual gradient -- against autograd through LayerNorm -> ff and against the two launches it replaces (tb_ff_bwd + tb_layernorm_bwd)."""
@@ -132,7 +132,7 @@ def test_ff_backward_with_the_layernorm_backward_in_its_epilogue(M):
     parity("ff_bwd + LayerNorm backward", dres, xr.grad + dy.float(), 2e-3, 3e-3, ch_dim=1, ch_rel=3e-3)
 
 
-@pytest.mark.parametrize("M,mode", [(128, 3), (384, 1), (384, 2), (4096, 3), (32768, 3)])
+@pytest.mark.parametrize("M,mode", [(128, 3), (384, 1), (384, 2), (4096, 3), (32768, 3), (8 * 5184, 3), (2 * 5184, 3)])
 def test_ff_forward_with_its_row_local_neighbours_in_the_same_launch(M, mode):
     """round 6 (tb_ff_desc.pre_W / post_W): attn2.to_out + residual + norm3 in FRONT of the fused feed-forward (mode bit 1) and proj_out + the block
     input BEHIND it (bit 2) -- diffusers BasicTransformerBlock / Transformer2DModel, train_textboost.py:1063-1067 -- against torch fp32 on the same
@@ -205,7 +205,8 @@ def test_ff_fused_rejects_what_it_does_not_cover():
     assert L.lib().tb_ff_fwd(d, None) == -22 and L.lib().tb_ff_bwd(d, None) == -22
 
 
-@pytest.mark.parametrize("M,N2,with_r", [(128, 320, True), (384, 960, False), (4096, 320, False), (32768, 960, False), (32768, 320, True)])
+@pytest.mark.parametrize("M,N2,with_r", [(128, 320, True), (384, 960, False), (4096, 320, False), (32768, 960, False), (32768, 320, True),
+                                         (8 * 5184, 960, False), (8 * 5184, 320, True)])
 def test_linear_layernorm_linear_in_one_launch(M, N2, with_r):
     """round 6 (tb_chain320, csrc/chain320.hip): proj_in -> norm1 -> attn1.qkv (N2 = 960) and attn1.to_out + residual -> norm2 -> attn2.to_q (N2 = 320)
     of a 64x64-map transformer block (diffusers Transformer2DModel / BasicTransformerBlock, train_textboost.py:1063-1067) as ONE launch -- against torch

@@ -103,7 +103,11 @@ def pack_conv_w_dgrad(w):  # -> [Cin, 9*Cout] with k = (ky*3+kx)*Cout + co
     return w.permute(1, 2, 3, 0).reshape(w.shape[1], -1).contiguous()
 
 
-@pytest.mark.parametrize("B,Cin,Cout,H,W", [(2, 64, 128, 16, 16), (1, 320, 320, 24, 20), (2, 128, 64, 7, 9)])
+@pytest.mark.parametrize("B,Cin,Cout,H,W", [(2, 64, 128, 16, 16), (1, 320, 320, 24, 20), (2, 128, 64, 7, 9),
+                                            # off the 8 * 2^k grid (72x72 / 40x40 latents): 9x9 / 5x5 mid-level maps, 36x36 level-1 maps
+                                            (1, 1280, 1280, 9, 9), (8, 1280, 1280, 9, 9), (1, 2560, 1280, 9, 9), (8, 2560, 1280, 9, 9),
+                                            (1, 2560, 1280, 5, 5), (4, 1280, 1280, 5, 5), (8, 2560, 1280, 5, 5),
+                                            (1, 640, 640, 36, 36), (8, 640, 640, 36, 36)])
 def test_conv3x3_fwd_and_dgrad(B, Cin, Cout, H, W):
     ops, L = _ops()
     torch.manual_seed(4)
@@ -156,6 +160,35 @@ def test_conv3x3_upsample_folded():
     ops.gemm(nhwc(x).view(-1, Cc), pack_conv_w(w), out, conv=geo)
     ref = F.conv2d(F.interpolate(x.float(), scale_factor=2.0, mode="nearest"), w.float(), padding=1)
     assert rel_err(out.view(B, 2 * H, 2 * W, Cc), nhwc(ref)) < 2e-3
+
+
+@pytest.mark.parametrize("B,C,H", [(1, 1280, 18), (8, 1280, 18), (8, 320, 72)])
+def test_conv3x3_stride2_and_upsample_onto_odd_map_sides(B, C, H):
+    """the downsampler (stride 2, H -> H/2) and upsampler (nearest x2 folded into the gather, H/2 -> H) convolutions of 72x72 latents, where the
+    coarse map side is odd (18 -> 9, 9 -> 18) or the fine one is not a multiple of 16 (72): forward, and the stride-2 transposed dgrad"""
+    ops, L = _ops()
+    torch.manual_seed(H + C)
+    Hc = H // 2
+    x = torch.randn(B, C, H, H, device="cuda").half()
+    w = (torch.randn(C, C, 3, 3, device="cuda") / (3 * C ** 0.5)).half()
+    bias = torch.randn(C, device="cuda")
+    out = torch.empty(B * Hc * Hc, C, device="cuda", dtype=torch.float16)
+    geo = dict(B=B, Hin=H, Win=H, Cin=C, Hout=Hc, Wout=Hc, stride=2, sign=1, upsample=0, transposed=0)
+    ops.gemm(nhwc(x).view(-1, C), pack_conv_w(w), out, bias=bias, conv=geo)
+    ref = F.conv2d(x.float(), w.float(), bias, stride=2, padding=1)
+    assert rel_err(out.view(B, Hc, Hc, C), nhwc(ref)) < 2e-3
+    dy = torch.randn(B, C, Hc, Hc, device="cuda").half()
+    dx = torch.empty(B * H * H, C, device="cuda", dtype=torch.float16)
+    geo = dict(B=B, Hin=Hc, Win=Hc, Cin=C, Hout=H, Wout=H, stride=1, sign=1, upsample=0, transposed=1)
+    ops.gemm(nhwc(dy).view(-1, C), pack_conv_w_dgrad(w), dx, conv=geo)
+    ref = F.conv_transpose2d(dy.float(), w.float(), stride=2, padding=1, output_padding=1)
+    assert rel_err(dx.view(B, H, H, C), nhwc(ref)) < 2e-3
+    xc = torch.randn(B, C, Hc, Hc, device="cuda").half()
+    up = torch.empty(B * H * H, C, device="cuda", dtype=torch.float16)
+    geo = dict(B=B, Hin=Hc, Win=Hc, Cin=C, Hout=H, Wout=H, stride=1, sign=1, upsample=1, transposed=0)
+    ops.gemm(nhwc(xc).view(-1, C), pack_conv_w(w), up, bias=bias, conv=geo)
+    ref = F.conv2d(F.interpolate(xc.float(), scale_factor=2.0, mode="nearest"), w.float(), bias, padding=1)
+    assert rel_err(up.view(B, H, H, C), nhwc(ref)) < 2e-3
 
 
 def test_gemm_rejects_bad_args():
@@ -360,7 +393,8 @@ def test_conv3x3_wide_tile_split_k(B, Cin, Cout, H):
     assert rel_err(dx.view(B, H, H, Cin), refd) < 2e-3
 
 
-@pytest.mark.parametrize("M,K,res", [(32768, 320, True), (32768, 960, False), (16384, 320, True), (25600, 640, True)])
+@pytest.mark.parametrize("M,K,res", [(32768, 320, True), (32768, 960, False), (16384, 320, True), (25600, 640, True),
+                                     (8 * 5184, 320, True), (2 * 6400, 320, True)])   # (8 x 72x72 maps; 2 x 80x80: exactly 200 64-row tiles)
 def test_layernorm_fused_into_the_linear_epilogue_forward(M, K, res):
     """TB_ACT_LN_FWD (round 3): the Linear that produces the residual stream also writes LayerNorm(row) and its statistics -- against
     torch.nn.functional.layer_norm of the fp16 row it stored, and against the separate tb_layernorm_fwd launch.  128 x 320 tiles (M / 128 >= 200)
@@ -395,7 +429,7 @@ def test_layernorm_fused_into_the_linear_epilogue_forward(M, K, res):
     assert (y.float() - y2.float()).abs().max().item() <= 2e-3 * y2.float().abs().max().item()   # one fp16 ulp where a value sits on a rounding edge
 
 
-@pytest.mark.parametrize("M,K,res", [(32768, 320, True), (32768, 2560, True), (16384, 960, False)])
+@pytest.mark.parametrize("M,K,res", [(32768, 320, True), (32768, 2560, True), (16384, 960, False), (8 * 5184, 2560, True), (2 * 6400, 320, True)])
 def test_layernorm_backward_fused_into_the_dgrad_epilogue(M, K, res):
     """TB_ACT_LN_BWD: dx = LN'(dy = A W^T) + add on the GEMM's accumulators, against torch autograd of layer_norm on the same operands."""
     from parity import parity
@@ -879,7 +913,7 @@ def test_linear_long_k_two_slices_of_128x160_tiles(K, bias, res):
     assert rel_err(outs[0], outs[1]) < 3e-4
 
 
-@pytest.mark.parametrize("M,C", [(8192, 640), (2048, 1280)])
+@pytest.mark.parametrize("M,C", [(8192, 640), (2048, 1280), (8 * 1296, 640), (2 * 1600, 640)])   # (8 x 36x36, 2 x 40x40 maps)
 def test_layernorm_folded_into_the_consuming_linear(M, C):
     """round 5 (tb_gemm_desc.rs_out / rs_in; torch.nn.LayerNorm norm1 / norm2 / norm3 of diffusers BasicTransformerBlock in front of attn1.to_q/k/v,
     attn2.to_q, ff.net.0.proj -- train_textboost.py:1063-1067): the producer of the residual stream writes per-column-tile (sum, sum of squares) of

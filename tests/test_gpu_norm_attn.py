@@ -24,7 +24,10 @@ def rel_err(a, b):
                                                (8, 256, 1280, True, 0), (4, 64, 2560, True, 0), (8, 256, 2560, False, 64), (8, 64, 1280, True, 0),
                                                # large maps, any even group width: the one-pass 1024-thread slice kernels (round 4)
                                                (8, 4096, 320, True, 0), (8, 1024, 640, True, 64), (8, 4096, 640, False, 0), (8, 1024, 1920, True, 0),
-                                               (8, 1024, 960, True, 64), (8, 4096, 960, True, 0), (4, 1000, 1280, True, 0), (16, 1024, 320, False, 0)])
+                                               (8, 1024, 960, True, 64), (8, 4096, 960, True, 0), (4, 1000, 1280, True, 0), (16, 1024, 320, False, 0),
+                                               # off the 8 * 2^k grid: 9x9 and 5x5 mid-level maps, 72x72 level-0 maps (72x72 / 40x40 latents)
+                                               (1, 81, 1280, True, 0), (8, 81, 2560, True, 0), (8, 81, 1280, False, 0), (4, 25, 1280, True, 0),
+                                               (4, 25, 2560, True, 0), (1, 5184, 320, True, 0), (8, 5184, 640, True, 0), (2, 5184, 960, False, 0)])
 def test_groupnorm_fwd_bwd(B, HW, C, silu, extra):
     ops = _ops()
     torch.manual_seed(0)
@@ -119,6 +122,33 @@ def ref_attention(q, k, v, H, causal):
     (1, 3, 77, 77, 64, False),
 ])
 def test_attention_fwd_bwd(B, H, Sq, Skv, hd, causal):
+    ws = 8 * 2 * B * Skv * H * hd if Skv <= 128 else None   # exercises the split-q path
+    _attention_fwd_bwd(B, H, Sq, Skv, hd, causal, ws)
+
+
+@pytest.mark.parametrize("B,H,Sq,Skv,hd", [
+    # SD1.x at 72x72 latents: 5184-token level-0 maps (5184 % 128 = 64: every fast path refused), 36x36 level-1 maps
+    (1, 8, 5184, 5184, 40), (2, 8, 5184, 5184, 40), (1, 8, 5184, 77, 40), (2, 8, 5184, 77, 40), (1, 8, 1296, 1296, 80),
+    # 80x80 latents: 40x40 level-1 maps (1600 % 128 = 64)
+    (2, 8, 1600, 1600, 80), (2, 8, 1600, 77, 80),
+    # 5x5 / 9x9 mid-block maps (40x40 / 72x72 latents): 25 self-attention keys (below the short-key paths), fewer queries than keys
+    (4, 8, 25, 25, 160), (4, 8, 25, 77, 160), (1, 8, 81, 77, 160),
+    # SD2.x at 72x72 latents: hd = 64 with the DMA-staged paths refused
+    (2, 5, 5184, 5184, 64), (2, 5, 5184, 77, 64),
+])
+def test_attention_fwd_bwd_at_off_grid_unet_shapes(B, H, Sq, Skv, hd):
+    """the layer shapes of latent sizes off the tuned 8 * 2^k grid, with the backward workspace the UNet passes for that layer
+    (textboost_amd/unet.py HipUNet._transformer: 16 query slices of fp32 dK / dV partials for cross-attention; 2 x [B, H, S] statistics for
+    hd 40 / 64 / 80 self-attention on S % 128 == 0 maps) -- so that the query-split and one-launch cross-attention paths run as in the model"""
+    C = H * hd
+    if Sq != Skv:
+        ws = 16 * 2 * B * Skv * C
+    else:
+        ws = 2 * B * H * Sq if hd in (40, 64, 80) and Sq % 128 == 0 else None
+    _attention_fwd_bwd(B, H, Sq, Skv, hd, False, ws)
+
+
+def _attention_fwd_bwd(B, H, Sq, Skv, hd, causal, ws_floats):
     ops = _ops()
     torch.manual_seed(2)
     C = H * hd
@@ -143,7 +173,7 @@ def test_attention_fwd_bwd(B, H, Sq, Skv, hd, causal):
     dq = torch.empty(B * Sq, C, device="cuda", dtype=torch.float16)
     dkv = torch.empty(B * Skv, 2 * C, device="cuda", dtype=torch.float16)
     dk, dv = dkv[:, :C], dkv[:, C:]
-    ws = torch.empty(8 * 2 * B * Skv * C, device="cuda") if Skv <= 128 else None   # exercises the split-q path
+    ws = torch.empty(ws_floats, device="cuda") if ws_floats else None
     ops.attention_bwd(q, k, v, o, lse, do, delta, dq, dk, dv, B, H, Sq, Skv, hd, causal=causal, ws=ws)
     oref.backward(do.float().view(B, Sq, C))
     parity("attention dQ", dq.view(B, Sq, C), qr.grad, rel=4e-3, maxabs=6e-3, ch_dim=2, ch_rel=6e-3)
@@ -151,7 +181,8 @@ def test_attention_fwd_bwd(B, H, Sq, Skv, hd, causal):
     parity("attention dV", dv.reshape(B, Skv, C), vr.grad, rel=4e-3, maxabs=6e-3, ch_dim=2, ch_rel=6e-3)
 
 
-@pytest.mark.parametrize("B,H,Sq,Skv", [(1, 2, 256, 128), (1, 2, 256, 192), (2, 3, 512, 320), (1, 8, 1024, 1024), (2, 8, 4096, 4096)])
+@pytest.mark.parametrize("B,H,Sq,Skv", [(1, 2, 256, 128), (1, 2, 256, 192), (2, 3, 512, 320), (1, 8, 1024, 1024), (2, 8, 4096, 4096),
+                                            (1, 8, 6400, 6400)])   # (80x80 latents: 25 tiles of 256 queries)
 def test_attention_fwd_software_pipelined_kernel(B, H, Sq, Skv):
     """attn_fwd_il_kernel (hd = 40, Sq % 256 == 0, Skv % 64 == 0, >= 2 KV tiles: the SD1.x 64x64-map self-attention shape and its smaller
     relatives): two query groups per wave run half an iteration apart, so the pipeline's prologue (2 tiles), the 4-slot ring wrapping,
@@ -377,7 +408,8 @@ def test_attention_forward_fp8_pv(B, H, S, spread):
     assert torch.isfinite(o8).all()
 
 
-@pytest.mark.parametrize("B,H,S,hd", [(2, 8, 1024, 40), (8, 8, 512, 40), (1, 8, 4096, 40), (8, 8, 1024, 80), (2, 8, 1024, 80), (1, 5, 9216, 64), (8, 10, 1024, 64)])
+@pytest.mark.parametrize("B,H,S,hd", [(2, 8, 1024, 40), (8, 8, 512, 40), (1, 8, 4096, 40), (8, 8, 1024, 80), (2, 8, 1024, 80), (1, 5, 9216, 64), (8, 10, 1024, 64),
+                                         (2, 8, 6400, 40)])   # (80x80 latents)
 def test_attention_backward_dma_staged_dkv(B, H, S, hd):
     """the hd = 40 / 64 / 80 self-attention backward with a ws of 2 * B * H * S floats takes attn_bwd_dkv_dma_kernel (>= 512 key blocks): against fp32
     autograd and against the register-staged kernels (bits 128 / 256 of tb_attention_set_variant switch the DMA dK/dV / dQ kernels off)."""

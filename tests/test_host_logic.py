@@ -336,3 +336,32 @@ def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
     assert sample.shape == (b.DUMP_TABLE_SAMPLE_ROWS, D)
     rows = [int(np.flatnonzero((table[:V].float().numpy() == s).all(1))[0]) for s in sample[:8]]
     assert rows == sorted(rows) and all(i < V for i in rows)     # original rows only, in ascending order
+
+
+def test_unet_and_cli_refuse_latent_sizes_the_levels_cannot_halve(tmp_path, monkeypatch):
+    """HipUNet assumes that every level halves the map exactly (`hw` of forward, the stride-2 downsamplers, the x2 upsamplers): a latent side
+    that is not a multiple of 2 ** (levels - 1) -- 8 for SD1.x / SD2.x -- would launch the downsampler onto a 32-row map where the reference's
+    gives 33.  Both the executor and the CLI refuse it, before anything is packed or reaches the device."""
+    import train_textboost as T
+    from textboost_amd import models
+    from textboost_amd.unet import HipUNet, check_latent_size, latent_multiple
+    assert latent_multiple(models.SD15_UNET) == 8 and latent_multiple(models.SD21_UNET) == 8
+    msg = r"latent size 65x65 \(images of 520x520 pixels\) is not supported.*multiple of 8 \(image resolution a multiple of 64\)"
+    for geo in (models.SD15_UNET, models.SD21_UNET):
+        with pytest.raises(ValueError, match=msg):
+            HipUNet(geo, {}, 1, 65, 65, device="cpu")     # (an empty state dict: the check comes before any packing)
+        with pytest.raises(ValueError, match=r"latent size 64x68 "):
+            HipUNet(geo, {}, 2, 64, 68, device="cpu")
+    for side in (64, 72, 80, 96):                           # 512, 576, 640, 768 pixels
+        check_latent_size(models.SD15_UNET, side, side)
+        T.check_resolution(8 * side, models.SD15_UNET)
+
+    def no_device():
+        raise AssertionError("the resolution must be refused before the device is touched")
+    monkeypatch.setattr(torch.cuda, "is_available", no_device)
+    base = ["--pretrained_model_name_or_path", str(tmp_path / "sd15"), "--output_dir", str(tmp_path / "o"), "--max_train_steps", "1"]
+    with pytest.raises(ValueError, match=msg):
+        T.main(T.parse_args(base + ["--resolution", "520"]))
+    with pytest.raises(ValueError, match=r"--resolution 516 is not supported.*multiple of 64"):
+        T.main(T.parse_args(base + ["--resolution", "516"]))
+    assert not (tmp_path / "o").exists()

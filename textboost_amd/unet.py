@@ -72,6 +72,21 @@ class UNetGeometry:
         return self.num_heads if isinstance(self.num_heads, int) else self.num_heads[level]
 
 
+def latent_multiple(geo: UNetGeometry) -> int:
+    """every level below the first halves the map exactly (the stride-2 downsamplers, the x2 upsamplers, `hw` of HipUNet.forward): a latent
+    side must be a multiple of this -- 8 for SD1.x / SD2.x, i.e. images whose side is a multiple of 64.  diffusers' `upsample_size` handling
+    of odd maps is not implemented."""
+    return 2 ** (len(geo.block_out_channels) - 1)
+
+
+def check_latent_size(geo: UNetGeometry, height: int, width: int):
+    f = latent_multiple(geo)
+    if height <= 0 or width <= 0 or height % f or width % f:
+        raise ValueError(f"latent size {height}x{width} (images of {8 * height}x{8 * width} pixels) is not supported: the UNet halves the map "
+                         f"{len(geo.block_out_channels) - 1} times, so the latent side must be a multiple of {f} (image resolution a multiple "
+                         f"of {8 * f})")
+
+
 def _f16(t, dtype=None):
     return t.detach().to(L.half_dtype() if dtype is None else dtype)
 
@@ -114,6 +129,7 @@ class HipUNet:
                  text_len: int = 77, device="cuda", attn_fp8: bool = False, dtype=None):
         """dtype = torch.float16: the reference's --mixed_precision fp16 run (`unet.to(accelerator.device, dtype=weight_dtype)`, :937);
         torch.float32: its default no-AMP run (:298-308, :930-939) -- every weight, activation and gradient fp32 (csrc/f32_path.hip)."""
+        check_latent_size(geo, height, width)   # (before anything is packed or allocated)
         dtype = L.half_dtype() if dtype is None else dtype   # (the active library's 16-bit float: fp16, or bf16 after _lib.set_half("bf16"))
         assert dtype in (L.half_dtype(), torch.float32)
         self.geo, self.B, self.H, self.W, self.T, self.dev = geo, batch, height, width, text_len, device

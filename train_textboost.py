@@ -72,10 +72,31 @@ def load_local_state_dict(path):
     return load_file(path) if os.path.exists(path) else None
 
 
+def check_resolution(resolution, unet_geo):
+    """--resolution is the image side; the latent side (resolution / 8) must survive every halving of the UNet exactly (textboost_amd.unet.
+    check_latent_size, which also catches a latent size taken from latents.pt / pixel_values.pt)."""
+    from textboost_amd.unet import check_latent_size, latent_multiple
+    if resolution % 8:
+        f = latent_multiple(unet_geo)
+        raise ValueError(f"--resolution {resolution} is not supported: the image side must be a multiple of {8 * f} (the VAE's factor 8 times "
+                         f"the UNet's {f})")
+    check_latent_size(unet_geo, resolution // 8, resolution // 8)
+
+
 def main(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    # ---- the architecture (from_pretrained reads it from the model directory, SD1.x or SD2.x): read first, so that a resolution the UNet cannot
+    # run is refused before anything reaches the device
+    mdir = args.pretrained_model_name_or_path
+    unet_geo, clip_geo = models.SD15_UNET, models.SD15_CLIP
+    ucfg, ccfg = os.path.join(mdir, "unet", "config.json"), os.path.join(mdir, "text_encoder", "config.json")
+    if os.path.exists(ucfg):
+        unet_geo = models.unet_geometry_from_config(json.load(open(ucfg)))
+    if os.path.exists(ccfg):
+        clip_geo = models.clip_geometry_from_config(json.load(open(ccfg)))
+    check_resolution(args.resolution, unet_geo)
     if not torch.cuda.is_available():
         raise SystemExit("train_textboost.py needs an MI355X: the product path has no CPU fallback")
     torch.cuda.set_device(local)
@@ -103,15 +124,8 @@ def main(args):
     from textboost_amd.workload import BOS, EOS, synthetic_ids
 
     # ---- models (:629-656)
-    mdir = args.pretrained_model_name_or_path
     usd = load_local_state_dict(os.path.join(mdir, "unet", "diffusion_pytorch_model.safetensors")) if os.path.isdir(mdir) else None
     csd = load_local_state_dict(os.path.join(mdir, "text_encoder", "model.safetensors")) if os.path.isdir(mdir) else None
-    unet_geo, clip_geo = models.SD15_UNET, models.SD15_CLIP
-    ucfg, ccfg = os.path.join(mdir, "unet", "config.json"), os.path.join(mdir, "text_encoder", "config.json")
-    if os.path.exists(ucfg):  # from_pretrained reads the architecture from the model directory (SD1.x, SD2.x): so does this
-        unet_geo = models.unet_geometry_from_config(json.load(open(ucfg)))
-    if os.path.exists(ccfg):
-        clip_geo = models.clip_geometry_from_config(json.load(open(ccfg)))
     if usd is None or csd is None:
         logger.warning("no local weights under %s: seeded random-init SD1.5 / CLIP-L shapes are used", mdir)
         usd = models.random_state_dict(models.unet_shapes(unet_geo), 1234, device=dev)
