@@ -1,0 +1,185 @@
+#!/usr/bin/env python3
+"""CLIP-T / CLIP-I evaluation of generated DreamBooth images: the reference's eval_dreambooth.py (`clip_score` :353-374, `clip_i` :377-453, the
+CSV of `main` :568-628) with the same flags, on the HIP CLIP ViT-L/14 of textboost_amd/clip_score.py.
+
+    python eval_dreambooth.py <path> --skip-gen --metric clip-t clip-i --clip-model <CLIPModel dir> \
+        [--outdir ./benchmarks] [--seeds 0 1 2 3] [--train-dir ...] [--val-dir ...] [--checkpoint N] [--output-desc D]
+
+Images are read from `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/*.png` (the reference's `generate()` with
+--skip-gen); the scores go to `<path>/metric{_ckpt<N>|_last}{_<desc>}.csv` in the reference's format.  --clip-model names a local transformers
+`CLIPModel` directory (config.json, model.safetensors, vocab.json, merges.txt): it replaces the reference's download of ViT-L/14@336px.
+
+Not built here: image generation (a run without --skip-gen), the VQA score (FlanT5-XXL) and the DINO score (DINOv2): asking for them is an error,
+so that a 0.000 placeholder in the CSV never reads as a score."""
+from __future__ import annotations
+
+import argparse
+import csv
+import glob
+import os
+import sys
+from typing import Dict, List, Optional
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+METRIC_KEYS = ("clip_score", "vqa_score", "clip_i", "clip_i_unseen", "dino", "dino_unseen")   # eval_dreambooth.py:575-586, CSV column order
+BUILT_METRICS = ("clip-t", "clip-i")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("path", type=str, help="path to model")
+    p.add_argument("--token-format", type=str, default="<INSTANCE> SUBJECT", help="prompt token format (image generation only)")
+    p.add_argument("--outdir", type=str, default="./benchmarks")
+    p.add_argument("--checkpoint", type=int, default=None)
+    p.add_argument("--instances", type=str, nargs="+", default=None)
+    p.add_argument("--skip-gen", action="store_true")
+    p.add_argument("--metric", type=str, nargs="+", default=["clip-t", "clip-i", "vqa"])
+    p.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
+    p.add_argument("--dreambooth-path", type=str, default="./data/dreambooth")
+    p.add_argument("--train-dir", type=str, default="./data/dreambooth_n1_train")
+    p.add_argument("--val-dir", type=str, default="./data/dreambooth_n1_val")
+    p.add_argument("--model", type=str, default=None)
+    p.add_argument("--output-desc", type=str, default=None)
+    p.add_argument("--clip-model", type=str, default=None, help="local transformers CLIPModel directory (ViT-L/14@336px) with its tokenizer files")
+    p.add_argument("--batch-size", type=int, default=32, help="images per tower launch")
+    return p
+
+
+def check_args(args):
+    """the refusals, before anything touches the device"""
+    if not args.skip_gen:
+        raise SystemExit("eval_dreambooth.py: image generation from a trained output directory is not built; generate the images elsewhere "
+                         "and pass --skip-gen")
+    unknown = [m for m in args.metric if m not in BUILT_METRICS + ("vqa", "dino")]
+    if unknown:
+        raise SystemExit(f"eval_dreambooth.py: unknown --metric {unknown}")
+    missing = [m for m in args.metric if m not in BUILT_METRICS]
+    if missing:
+        raise SystemExit(f"eval_dreambooth.py: --metric {' '.join(missing)} is not built (only CLIP-T and CLIP-I are); "
+                         "pass --metric clip-t clip-i")
+    if not args.clip_model:
+        raise SystemExit("eval_dreambooth.py: --clip-model DIR (a local CLIPModel directory) is required")
+    if args.batch_size <= 0:
+        raise SystemExit("eval_dreambooth.py: --batch-size must be positive")
+
+
+def image_root(args) -> str:
+    """eval_dreambooth.py `generate()` with --skip-gen"""
+    path = args.path.rstrip("/") or args.path
+    outdir = args.outdir.rstrip("/") or args.outdir
+    base = os.path.basename(path)
+    if args.checkpoint is not None:
+        base = f"{base}-{args.checkpoint}"
+    root = os.path.join(outdir, base)
+    if args.output_desc is not None:
+        root += f"_{args.output_desc}"
+    return root
+
+
+def csv_path(args) -> str:
+    ckpt = f"_ckpt{args.checkpoint}" if args.checkpoint is not None else "_last"
+    desc = f"_{args.output_desc}" if args.output_desc is not None else ""
+    return os.path.join(args.path.rstrip("/") or args.path, f"metric{ckpt}{desc}.csv")
+
+
+def generated_images(seed_dir: str, instances: Optional[List[str]]) -> Dict[str, List[str]]:
+    """instance -> sorted *.png of seed_dir/<instance>/ (every instance directory there, or the --instances among them)"""
+    if not os.path.isdir(seed_dir):
+        raise SystemExit(f"eval_dreambooth.py: {seed_dir} does not exist")
+    names = sorted(d for d in os.listdir(seed_dir) if os.path.isdir(os.path.join(seed_dir, d)))
+    if instances is not None:
+        names = [n for n in names if n in instances]
+    out = {n: sorted(glob.glob(os.path.join(seed_dir, n, "*.png"))) for n in names}
+    out = {n: v for n, v in out.items() if v}
+    if not out:
+        raise SystemExit(f"eval_dreambooth.py: no generated images under {seed_dir}/<instance>/*.png")
+    return out
+
+
+def real_images(root: str, instances, flag: str) -> Dict[str, List[str]]:
+    """instance -> sorted real images `root/<instance>/*.*` (eval_dreambooth.py:389-390); every instance must have some"""
+    out = {}
+    for inst in instances:
+        files = sorted(f for f in glob.glob(os.path.join(root, inst, "*.*")) if os.path.isfile(f))
+        if not files:
+            raise SystemExit(f"eval_dreambooth.py: no images for instance {inst!r} in {flag} {root}")
+        out[inst] = files
+    return out
+
+
+def format_row(seed, scores: Dict[str, "object"]) -> List[str]:
+    """eval_dreambooth.py:620-626: the seed, then every metric's mean as %.3f (0.000 for one that was not asked for)"""
+    row = [str(seed)]
+    for k in METRIC_KEYS:
+        v = scores.get(k)
+        row.append(f"{float(v.float().mean().item()) if v is not None else 0.0:.3f}")
+    return row
+
+
+def clip_i_means(gen_emb: Dict[str, "object"], real_emb: Dict[str, "object"]):
+    """concatenated max(cos, 0) over instances (eval_dreambooth.py:426-449)"""
+    import torch
+    from textboost_amd.clip_score import clip_i_scores
+    return torch.cat([clip_i_scores(gen_emb[k], real_emb[k]) for k in gen_emb])
+
+
+def evaluate(args, evaluator=None):
+    """-> {seed: {metric: per-sample scores}}; writes the CSV."""
+    from textboost_amd.clip_score import CLIPEvaluator, clip_t_scores, prompt_of
+    root = image_root(args)
+    per_seed = {s: generated_images(os.path.join(root, f"seed{s}"), args.instances) for s in args.seeds}
+    instances = sorted({i for g in per_seed.values() for i in g})
+    seen = unseen = None
+    if "clip-i" in args.metric:
+        seen = real_images(args.train_dir, instances, "--train-dir")
+        unseen = real_images(args.val_dir, instances, "--val-dir")
+    ev = evaluator or CLIPEvaluator(args.clip_model, batch_size=args.batch_size)
+    real_emb = {}
+    if seen is not None:   # every real image once per run (the reference encodes them again for every seed)
+        for name, table in (("seen", seen), ("unseen", unseen)):
+            flat = [p for i in instances for p in table[i]]
+            emb = ev.encode_images(flat, clip_i=True)
+            off, real_emb[name] = 0, {}
+            for i in instances:
+                real_emb[name][i] = emb[off:off + len(table[i])]
+                off += len(table[i])
+    results = {}
+    for s in args.seeds:
+        gen = per_seed[s]
+        paths = [p for i in sorted(gen) for p in gen[i]]
+        scores = {}
+        if "clip-t" in args.metric:
+            scores["clip_score"] = clip_t_scores(ev.encode_images(paths, clip_i=False), ev.encode_texts([prompt_of(p) for p in paths]))
+            print(f"[seed {s}] CLIP-T: {scores['clip_score'].mean():.3f} +/- {scores['clip_score'].std():.3f} ({len(paths)} images)")
+        if "clip-i" in args.metric:
+            emb = ev.encode_images(paths, clip_i=True)
+            gen_emb, off = {}, 0
+            for i in sorted(gen):
+                gen_emb[i] = emb[off:off + len(gen[i])]
+                off += len(gen[i])
+            scores["clip_i"] = clip_i_means(gen_emb, real_emb["seen"])
+            scores["clip_i_unseen"] = clip_i_means(gen_emb, real_emb["unseen"])
+            print(f"[seed {s}] CLIP-I (seen): {scores['clip_i'].mean():.3f}  CLIP-I (unseen): {scores['clip_i_unseen'].mean():.3f}")
+        results[s] = scores
+    out = csv_path(args)
+    with open(out, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["seed"] + list(METRIC_KEYS))
+        for s in args.seeds:
+            w.writerow(format_row(s, results[s]))
+    print(f"image tower: {ev.tower_images} images, {ev.images_per_second():.1f} images/s ({ev.geo.image_size} px, batch {ev.batch_size})")
+    print(f"wrote {out}")
+    return results
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    check_args(args)
+    return evaluate(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -473,6 +473,8 @@ int tb_mse_loss_f32(const float* pred, const float* target, float* dpred, float*
  * The three table builders run on the HOST (plain host pointers, O(W + H) work); everything else takes device pointers + a stream. */
 #define TB_IMG_LANCZOS 1 /* PIL.Image.Resampling ids */
 #define TB_IMG_BICUBIC 3
+/* Pillow's BILINEAR (triangle, support 1).  Not Pillow's id 2: the ids this ABI refused before it existed (2, 4, 5) stay refused */
+#define TB_IMG_BILINEAR 16
 /* Resample.c precompute_coeffs + normalize_coeffs_8bpc for a full-width box: returns ksize (odd), or a negative error */
 int tb_resample_ksize(int in_size, int out_size, int filter);
 int tb_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds /* host [out_size * 2]: (first, count) */,
@@ -498,6 +500,15 @@ int tb_img_to_pixels(const uint32_t* src, int64_t sstride, int sw, int sh, int x
 /* RGB u8 [n][3] -> RGBX, and back ([h][w][3]) */
 int tb_img_pack_rgb(const uint8_t* rgb, uint32_t* dst, int64_t n_pixels, tb_stream_t stream);
 int tb_img_unpack_rgb(const uint32_t* src, int64_t sstride, int w, int h, uint8_t* rgb, tb_stream_t stream);
+
+/* ---- CLIP ViT patch embedding (csrc/clip_vision.hip; the image tower of the CLIP-T / CLIP-I evaluation, textboost_amd/clip_score.py) -------
+ * img: B resident RGBX images of S x S pixels, image b at img + b * img_stride, rows row_stride pixels apart.  P = (S / patch)^2 patches.
+ * w: TB_F16 [D][ldw], K = 4 patch^2 columns in the order (ky, kx, R G B X) then zeros up to Kp (a multiple of 32): the conv weight with
+ * CLIP's Normalize folded in (W / (255 std_c); the X column zero), bias fp32 [D] = -sum W mean_c / std_c.  cls fp32 [D], pos fp32 [1 + P][D].
+ * out fp32 rows [B * (1 + P)][ldo]: row b (1 + P) = cls + pos[0], row b (1 + P) + 1 + p = patch p . W' + bias + pos[1 + p].
+ * patch even, S % patch == 0, D % 16 == 0. */
+int tb_clip_patch_embed(const uint32_t* img, int64_t img_stride, int64_t row_stride, int B, int S, int patch, const void* w, int64_t ldw,
+                        int Kp, const float* bias, const float* cls, const float* pos, float* out, int64_t ldo, int D, tb_stream_t stream);
 
 #ifdef __cplusplus
 }

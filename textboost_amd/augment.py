@@ -27,7 +27,7 @@ import torch
 from . import _lib as L
 from . import ops
 
-NEAREST, LANCZOS, BICUBIC = 0, L.IMG_LANCZOS, L.IMG_BICUBIC
+NEAREST, LANCZOS, BILINEAR, BICUBIC = 0, L.IMG_LANCZOS, L.IMG_BILINEAR, L.IMG_BICUBIC
 
 # resample tables per (in, out, filter, device): an LRU, because `crop` draws a new source size for almost every sample
 _coeff_cache: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict()

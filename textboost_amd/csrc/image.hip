@@ -3,7 +3,7 @@
 //
 // Layout: an image is RGBX u8, one uint32 per pixel ([H][stride] pixels, R in the low byte) -- every access is a naturally aligned dword, so a
 // wave reads 256 contiguous bytes per row segment.  All kernels are HBM-bound byte work (no MFMA); results are BIT-EXACT with Pillow:
-//   * tb_img_resample      Image.resize (libImaging Resample.c): one separable pass, 22-bit fixed-point coefficients, 8-bit intermediate
+//   * tb_img_resample      Image.resize (libImaging Resample.c; BILINEAR, BICUBIC, LANCZOS): one separable pass, 22-bit fixed-point coefficients, 8-bit intermediate
 //   * tb_img_gather        every separable index map: crop, edge / zero pad, horizontal flip, collage tiling, the NEAREST affine
 //                          (ImagingScaleAffine's pretabulated columns / rows), optional convert("L") luma
 //   * tb_img_affine_bicubic Image.transform(AFFINE, BICUBIC) (Geometry.c bicubic_filter32RGB) in fp64 with no contraction, fused with the
@@ -29,6 +29,11 @@ static inline double bicubic_filter_h(double x) {
   if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
   return 0.0;
 }
+static inline double bilinear_filter_h(double x) {
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return 1.0 - x;
+  return 0.0;
+}
 static inline double sinc_filter_h(double x) {
   if (x == 0.0) return 1.0;
   x = x * M_PI;
@@ -40,7 +45,7 @@ static inline double lanczos_filter_h(double x) {
 }
 
 static int resample_ksize(int in_size, int out_size, int filter, double* support_out, double* scale_out) {
-  double fsupport = filter == TB_IMG_BICUBIC ? 2.0 : 3.0;
+  double fsupport = filter == TB_IMG_BILINEAR ? 1.0 : filter == TB_IMG_BICUBIC ? 2.0 : 3.0;
   double scale = (double)((float)in_size - 0.0f) / out_size;
   double filterscale = scale < 1.0 ? 1.0 : scale;
   double support = fsupport * filterscale;
@@ -49,13 +54,15 @@ static int resample_ksize(int in_size, int out_size, int filter, double* support
   return (int)ceil(support) * 2 + 1;
 }
 
+static bool known_filter(int filter) { return filter == TB_IMG_BILINEAR || filter == TB_IMG_BICUBIC || filter == TB_IMG_LANCZOS; }
+
 extern "C" int tb_resample_ksize(int in_size, int out_size, int filter) {
-  if (in_size <= 0 || out_size <= 0 || (filter != TB_IMG_BICUBIC && filter != TB_IMG_LANCZOS)) return TB_EINVAL;
+  if (in_size <= 0 || out_size <= 0 || !known_filter(filter)) return TB_EINVAL;
   return resample_ksize(in_size, out_size, filter, nullptr, nullptr);
 }
 
 extern "C" int tb_resample_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk) {
-  if (in_size <= 0 || out_size <= 0 || (filter != TB_IMG_BICUBIC && filter != TB_IMG_LANCZOS) || !bounds || !kk) return TB_EINVAL;
+  if (in_size <= 0 || out_size <= 0 || !known_filter(filter) || !bounds || !kk) return TB_EINVAL;
   double support, scale;
   int ksize = resample_ksize(in_size, out_size, filter, &support, &scale);
   double filterscale = scale < 1.0 ? 1.0 : scale;
@@ -72,7 +79,9 @@ extern "C" int tb_resample_coeffs(int in_size, int out_size, int filter, int32_t
     xmax -= xmin;
     for (int x = 0; x < xmax; x++) {
       double arg = (x + xmin - center + 0.5) * ss;
-      double w = filter == TB_IMG_BICUBIC ? bicubic_filter_h(arg) : lanczos_filter_h(arg);
+      double w = filter == TB_IMG_BILINEAR  ? bilinear_filter_h(arg)
+                 : filter == TB_IMG_BICUBIC ? bicubic_filter_h(arg)
+                                            : lanczos_filter_h(arg);
       k[x] = w;
       ww += w;
     }

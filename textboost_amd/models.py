@@ -11,6 +11,7 @@ from typing import Dict, Tuple
 
 import torch
 
+from .clip_score import CLIPVisionGeometry
 from .text_encoder import CLIPGeometry, HF_LAYER
 from .unet import UNetGeometry
 
@@ -19,6 +20,9 @@ SD21_UNET = UNetGeometry(num_heads=(5, 10, 20, 20), cross_attention_dim=1024, us
 SD15_CLIP = CLIPGeometry()
 # SD2.x text encoder: OpenCLIP ViT-H/14 text tower, 23 of its 24 layers (penultimate-layer output), erf-GELU MLP
 SD21_CLIP = CLIPGeometry(hidden_size=1024, intermediate_size=4096, num_layers=23, num_heads=16, act="gelu")
+# OpenAI CLIP ViT-L/14@336px, the model of the CLIP-T / CLIP-I evaluation (clip_score.py): its image tower and its CLIP-L text tower
+CLIP_VIT_L14_336 = CLIPVisionGeometry()
+CLIP_VIT_L14_TEXT = CLIPGeometry()
 
 
 def unet_shapes(geo: UNetGeometry) -> Dict[str, Tuple[int, ...]]:
@@ -102,6 +106,28 @@ def clip_shapes(geo: CLIPGeometry) -> Dict[str, Tuple[int, ...]]:
             S[p + HF_LAYER[n] + ".weight"] = (D, D); S[p + HF_LAYER[n] + ".bias"] = (D,)
         S[p + HF_LAYER["fc1"] + ".weight"] = (I, D); S[p + HF_LAYER["fc1"] + ".bias"] = (I,)
         S[p + HF_LAYER["fc2"] + ".weight"] = (D, I); S[p + HF_LAYER["fc2"] + ".bias"] = (D,)
+    return S
+
+
+def clip_model_shapes(vgeo: CLIPVisionGeometry, tgeo: CLIPGeometry) -> Dict[str, Tuple[int, ...]]:
+    """transformers `CLIPModel` state dict: both towers and both projections (no bias on the patch embedding and the projections)."""
+    D, I, p = vgeo.hidden_size, vgeo.intermediate_size, vgeo.patch_size
+    pre = "vision_model."
+    S = {pre + "embeddings.class_embedding": (D,), pre + "embeddings.patch_embedding.weight": (D, 3, p, p),
+         pre + "embeddings.position_embedding.weight": (1 + vgeo.num_patches, D)}
+    for n in ("pre_layrnorm", "post_layernorm"):
+        S[f"{pre}{n}.weight"] = (D,); S[f"{pre}{n}.bias"] = (D,)
+    for i in range(vgeo.num_layers):
+        lp = f"{pre}encoder.layers.{i}."
+        for n in ("ln1", "ln2"):
+            S[lp + HF_LAYER[n] + ".weight"] = (D,); S[lp + HF_LAYER[n] + ".bias"] = (D,)
+        for n in ("q", "k", "v", "out"):
+            S[lp + HF_LAYER[n] + ".weight"] = (D, D); S[lp + HF_LAYER[n] + ".bias"] = (D,)
+        S[lp + HF_LAYER["fc1"] + ".weight"] = (I, D); S[lp + HF_LAYER["fc1"] + ".bias"] = (I,)
+        S[lp + HF_LAYER["fc2"] + ".weight"] = (D, I); S[lp + HF_LAYER["fc2"] + ".bias"] = (D,)
+    S["visual_projection.weight"] = (vgeo.projection_dim, D)
+    S.update(clip_shapes(tgeo))
+    S["text_projection.weight"] = (vgeo.projection_dim, tgeo.hidden_size)
     return S
 
 

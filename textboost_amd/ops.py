@@ -911,3 +911,20 @@ def img_unpack_rgb(img):
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
     L.check(L.lib().tb_img_unpack_rgb(L.ptr(img), img.stride(0), w, h, L.ptr(out), L.stream()), "tb_img_unpack_rgb")
     return out
+
+
+# ------------------------------------------------------------------------------------------- CLIP ViT patch embedding (clip_score.py)
+def clip_patch_embed(images, patch, w_packed, bias, cls, pos, out):
+    """images: int32 RGBX [B, S, S(+)] (rows / images may be strided); w_packed: half [D, Kp] from clip_score.pack_patch_weight; bias, cls fp32 [D];
+    pos fp32 [1 + P, D].  out: fp32 [B * (1 + P), D] (row stride >= D) <- class row + patch rows, position embeddings added."""
+    B, S, _ = images.shape
+    D = w_packed.shape[0]
+    assert images.dtype == torch.int32 and images.stride(2) == 1 and w_packed.dtype == L.half_dtype() and w_packed.stride(1) == 1
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (bias, cls, pos)) and out.dtype == torch.float32 and out.stride(1) == 1
+    P = (S // patch) ** 2
+    assert pos.shape == (1 + P, D) and bias.shape == (D,) and cls.shape == (D,) and out.shape == (B * (1 + P), D)
+    with _rec("clip_patch_embed_kernel", 2.0 * B * P * D * w_packed.shape[1], float(images.numel() * 4 + w_packed.numel() * 2 + out.numel() * 4)):
+        L.check(L.lib().tb_clip_patch_embed(L.ptr(images), images.stride(0), images.stride(1), B, S, patch, L.ptr(w_packed), w_packed.stride(0),
+                                            w_packed.shape[1], L.ptr(bias), L.ptr(cls), L.ptr(pos), L.ptr(out), out.stride(0), D, L.stream()),
+                "tb_clip_patch_embed")
+    return out
