@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
-"""CLIP-T / CLIP-I evaluation of generated DreamBooth images: the reference's eval_dreambooth.py (`clip_score` :353-374, `clip_i` :377-453, the
-CSV of `main` :568-628) with the same flags, on the HIP CLIP ViT-L/14 of textboost_amd/clip_score.py.
+"""CLIP-T / CLIP-I / DINO evaluation of generated DreamBooth images: the reference's eval_dreambooth.py (`clip_score` :353-374, `clip_i`
+:377-453, `dino_score` :456-543, the CSV of `main` :568-628) with the same flags, on the HIP CLIP ViT-L/14 of textboost_amd/clip_score.py and
+the HIP DINOv2 ViT-L/14 of textboost_amd/dino_score.py.
 
-    python eval_dreambooth.py <path> --skip-gen --metric clip-t clip-i --clip-model <CLIPModel dir> \
-        [--outdir ./benchmarks] [--seeds 0 1 2 3] [--train-dir ...] [--val-dir ...] [--checkpoint N] [--output-desc D]
+    python eval_dreambooth.py <path> --skip-gen --metric clip-t clip-i dino --clip-model <CLIPModel dir> --dino-model <DINOv2 weights> \
+        [--outdir ./benchmarks] [--seeds 0 1 2 3] [--train-dir ...] [--val-dir ...] [--dreambooth-path ./data/dreambooth] [--checkpoint N]
+        [--output-desc D]
 
 Images are read from `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/*.png` (the reference's `generate()` with
 --skip-gen); the scores go to `<path>/metric{_ckpt<N>|_last}{_<desc>}.csv` in the reference's format.  --clip-model names a local transformers
 `CLIPModel` directory (config.json, model.safetensors, vocab.json, merges.txt): it replaces the reference's download of ViT-L/14@336px.
+--dino-model names the hub's `dinov2_vitl14_pretrain.pth` or a local transformers `Dinov2Model` directory: it replaces the reference's
+`torch.hub.load('facebookresearch/dinov2', 'dinov2_vitl14')`.  DINO reads the real images from `<dreambooth-path>/<instance>/*.*` (sorted) and
+takes N, the number of seen ones, from `path` as the reference does (`<name>-<model>-n<N>`, e.g. `out/tb-sd15-n1`): an instance's first N real
+images are seen, the rest unseen.
 
-Not built here: image generation (a run without --skip-gen), the VQA score (FlanT5-XXL) and the DINO score (DINOv2): asking for them is an error,
-so that a 0.000 placeholder in the CSV never reads as a score."""
+Not built here: image generation (a run without --skip-gen) and the VQA score (FlanT5-XXL): asking for them is an error, so that a 0.000
+placeholder in the CSV never reads as a score."""
 from __future__ import annotations
 
 import argparse
@@ -25,7 +31,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 METRIC_KEYS = ("clip_score", "vqa_score", "clip_i", "clip_i_unseen", "dino", "dino_unseen")   # eval_dreambooth.py:575-586, CSV column order
-BUILT_METRICS = ("clip-t", "clip-i")
+BUILT_METRICS = ("clip-t", "clip-i", "dino")
 
 
 def build_parser():
@@ -44,6 +50,8 @@ def build_parser():
     p.add_argument("--model", type=str, default=None)
     p.add_argument("--output-desc", type=str, default=None)
     p.add_argument("--clip-model", type=str, default=None, help="local transformers CLIPModel directory (ViT-L/14@336px) with its tokenizer files")
+    p.add_argument("--dino-model", type=str, default=None,
+                   help="DINOv2 ViT-L/14 weights: the hub's dinov2_vitl14_pretrain.pth or a local transformers Dinov2Model directory")
     p.add_argument("--batch-size", type=int, default=32, help="images per tower launch")
     return p
 
@@ -53,15 +61,18 @@ def check_args(args):
     if not args.skip_gen:
         raise SystemExit("eval_dreambooth.py: image generation from a trained output directory is not built; generate the images elsewhere "
                          "and pass --skip-gen")
-    unknown = [m for m in args.metric if m not in BUILT_METRICS + ("vqa", "dino")]
+    unknown = [m for m in args.metric if m not in BUILT_METRICS + ("vqa",)]
     if unknown:
         raise SystemExit(f"eval_dreambooth.py: unknown --metric {unknown}")
     missing = [m for m in args.metric if m not in BUILT_METRICS]
     if missing:
-        raise SystemExit(f"eval_dreambooth.py: --metric {' '.join(missing)} is not built (only CLIP-T and CLIP-I are); "
-                         "pass --metric clip-t clip-i")
-    if not args.clip_model:
-        raise SystemExit("eval_dreambooth.py: --clip-model DIR (a local CLIPModel directory) is required")
+        raise SystemExit(f"eval_dreambooth.py: --metric {' '.join(missing)} is not built (only CLIP-T, CLIP-I and DINO are); "
+                         "pass --metric clip-t clip-i dino, or some of them")
+    if "dino" in args.metric and not args.dino_model:
+        raise SystemExit("eval_dreambooth.py: --metric dino needs --dino-model PATH (the hub's dinov2_vitl14_pretrain.pth or a local "
+                         "Dinov2Model directory)")
+    if any(m in args.metric for m in ("clip-t", "clip-i")) and not args.clip_model:
+        raise SystemExit("eval_dreambooth.py: --clip-model DIR (a local CLIPModel directory) is required for clip-t / clip-i")
     if args.batch_size <= 0:
         raise SystemExit("eval_dreambooth.py: --batch-size must be positive")
 
@@ -110,6 +121,37 @@ def real_images(root: str, instances, flag: str) -> Dict[str, List[str]]:
     return out
 
 
+def parse_n_seen(path: str) -> int:
+    """N, the number of seen real images per instance: eval_dreambooth.py:496 `int(args.path.split("-")[2].split("n")[-1])` on the path that
+    `main` left (one trailing '/' removed), e.g. `out/tb-sd15-n1` -> 1"""
+    p = path[:-1] if path.endswith("/") else path
+    try:
+        n = int(p.split("-")[2].split("n")[-1])
+    except (IndexError, ValueError):
+        raise SystemExit(f"eval_dreambooth.py: --metric dino takes N (the seen real images per instance) from the run path as the reference "
+                         f"does, `<name>-<model>-n<N>` with N after the second '-' (e.g. out/tb-sd15-n1); cannot parse {path!r}") from None
+    if n < 1:
+        raise SystemExit(f"eval_dreambooth.py: --metric dino: N = {n} seen real images (from {path!r}); it must be at least 1")
+    return n
+
+
+def dreambooth_images(root: str, instances, n_seen: int) -> Dict[str, List[str]]:
+    """instance -> its real images: `sorted(glob(<root>/**/*.*))` (eval_dreambooth.py:467; without recursive=True `**` matches one directory
+    level) grouped by parent directory.  Every instance in use needs more than N of them: the first N are the seen ones, the rest the unseen."""
+    by_instance: Dict[str, List[str]] = {}
+    for f in sorted(glob.glob(os.path.join(root, "*", "*.*"))):
+        if os.path.isfile(f):
+            by_instance.setdefault(os.path.basename(os.path.dirname(f)), []).append(f)
+    for inst in instances:
+        n = len(by_instance.get(inst, []))
+        if n == 0:
+            raise SystemExit(f"eval_dreambooth.py: no images for instance {inst!r} in --dreambooth-path {root}")
+        if n <= n_seen:
+            raise SystemExit(f"eval_dreambooth.py: instance {inst!r} has {n} real images in --dreambooth-path {root}; DINO needs more than "
+                             f"N = {n_seen} (the first N are seen, the rest unseen)")
+    return {inst: by_instance[inst] for inst in instances}
+
+
 def format_row(seed, scores: Dict[str, "object"]) -> List[str]:
     """eval_dreambooth.py:620-626: the seed, then every metric's mean as %.3f (0.000 for one that was not asked for)"""
     row = [str(seed)]
@@ -126,17 +168,42 @@ def clip_i_means(gen_emb: Dict[str, "object"], real_emb: Dict[str, "object"]):
     return torch.cat([clip_i_scores(gen_emb[k], real_emb[k]) for k in gen_emb])
 
 
-def evaluate(args, evaluator=None):
+def split_by_instance(emb, table: Dict[str, List[str]], instances) -> Dict[str, "object"]:
+    """rows of `emb` in the order of [p for i in instances for p in table[i]] -> instance -> its rows"""
+    out, off = {}, 0
+    for i in instances:
+        out[i] = emb[off:off + len(table[i])]
+        off += len(table[i])
+    return out
+
+
+def dino_means(gen_emb: Dict[str, "object"], real_emb: Dict[str, "object"], n_seen: int):
+    """(seen, unseen) per generated image, concatenated over instances (eval_dreambooth.py:512-537)"""
+    import torch
+    from textboost_amd.dino_score import dino_scores
+    pairs = [dino_scores(gen_emb[k], real_emb[k], n_seen) for k in gen_emb]
+    return torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
+
+
+def evaluate(args, evaluator=None, dino_evaluator=None):
     """-> {seed: {metric: per-sample scores}}; writes the CSV."""
     from textboost_amd.clip_score import CLIPEvaluator, clip_t_scores, prompt_of
     root = image_root(args)
     per_seed = {s: generated_images(os.path.join(root, f"seed{s}"), args.instances) for s in args.seeds}
     instances = sorted({i for g in per_seed.values() for i in g})
-    seen = unseen = None
+    seen = unseen = db = None
     if "clip-i" in args.metric:
         seen = real_images(args.train_dir, instances, "--train-dir")
         unseen = real_images(args.val_dir, instances, "--val-dir")
-    ev = evaluator or CLIPEvaluator(args.clip_model, batch_size=args.batch_size)
+    if "dino" in args.metric:
+        n_seen = parse_n_seen(args.path)
+        db = dreambooth_images(args.dreambooth_path, instances, n_seen)
+    ev = dev = None
+    if any(m in args.metric for m in ("clip-t", "clip-i")):
+        ev = evaluator or CLIPEvaluator(args.clip_model, batch_size=args.batch_size)
+    if db is not None:
+        from textboost_amd.dino_score import DINOEvaluator
+        dev = dino_evaluator or DINOEvaluator(args.dino_model, batch_size=args.batch_size)
     real_emb = {}
     if seen is not None:   # every real image once per run (the reference encodes them again for every seed)
         for name, table in (("seen", seen), ("unseen", unseen)):
@@ -146,6 +213,9 @@ def evaluate(args, evaluator=None):
             for i in instances:
                 real_emb[name][i] = emb[off:off + len(table[i])]
                 off += len(table[i])
+    dino_real = None
+    if db is not None:   # every real image once per run (the reference encodes them again for every seed)
+        dino_real = split_by_instance(dev.encode_images([p for i in instances for p in db[i]]), db, instances)
     results = {}
     for s in args.seeds:
         gen = per_seed[s]
@@ -163,6 +233,9 @@ def evaluate(args, evaluator=None):
             scores["clip_i"] = clip_i_means(gen_emb, real_emb["seen"])
             scores["clip_i_unseen"] = clip_i_means(gen_emb, real_emb["unseen"])
             print(f"[seed {s}] CLIP-I (seen): {scores['clip_i'].mean():.3f}  CLIP-I (unseen): {scores['clip_i_unseen'].mean():.3f}")
+        if dino_real is not None:
+            scores["dino"], scores["dino_unseen"] = dino_means(split_by_instance(dev.encode_images(paths), gen, sorted(gen)), dino_real, n_seen)
+            print(f"[seed {s}] DINO (seen): {scores['dino'].mean():.3f}  DINO (unseen): {scores['dino_unseen'].mean():.3f}")
         results[s] = scores
     out = csv_path(args)
     with open(out, "w", newline="") as f:
@@ -170,7 +243,10 @@ def evaluate(args, evaluator=None):
         w.writerow(["seed"] + list(METRIC_KEYS))
         for s in args.seeds:
             w.writerow(format_row(s, results[s]))
-    print(f"image tower: {ev.tower_images} images, {ev.images_per_second():.1f} images/s ({ev.geo.image_size} px, batch {ev.batch_size})")
+    if ev is not None:
+        print(f"image tower: {ev.tower_images} images, {ev.images_per_second():.1f} images/s ({ev.geo.image_size} px, batch {ev.batch_size})")
+    if dev is not None:
+        print(f"DINO tower: {dev.tower_images} images, {dev.images_per_second():.1f} images/s ({dev.geo.image_size} px, batch {dev.batch_size})")
     print(f"wrote {out}")
     return results
 

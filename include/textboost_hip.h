@@ -60,7 +60,7 @@ typedef struct tb_gemm_desc {
    *   upsample   : u = (y + ky-1, x + kx-1) in 2Hin x 2Win, src = u >> 1  (nearest x2 folded into the gather)
    *   transposed : dgrad of a stride-2 conv: src = ((y+1-ky)/2, (x+1-kx)/2) where both are even & in range */
   int32_t B, Hin, Win, Cin, Hout, Wout, stride, sign, upsample, transposed, shift;
-  /* epilogue: v = alpha*acc + bias[n] + rowbias[(m / rows_per_group)*N + n] + R[m,n]; v = act(v) */
+  /* epilogue: v = alpha*acc + bias[n] + rowbias[(m / rows_per_group)*N + n] + R[m,n]; v = act(v)   (col_scale: see the last field) */
   float alpha;
   const float* bias;             /* fp32 [N] or NULL */
   const float* rowbias;          /* fp32 [M/rows_per_group, N] or NULL (ResnetBlock2D time_emb_proj term) */
@@ -103,6 +103,12 @@ typedef struct tb_gemm_desc {
    *          the same in front of the gate for GEGLU; ln_gamma = c1 (fp32 [N], in W's row order), bias = c2.  When ln_stats != NULL the column
    *          tile 0 of every row panel writes (mean, rstd) to ln_stats[m] for tb_layernorm_bwd.  rs_n <= 16; no second K source. */
   float* rs_out; const float* rs_in; int64_t rs_ld; int32_t rs_n;
+  /* optional per-column scale of the Linear's output, fp32 [N] or NULL (DINOv2's LayerScale, textboost_amd/dino_score.py):
+   *     v = col_scale[n] * (alpha*acc + bias[n]) + R[m,n]        (the residual is not scaled)
+   * applied in fp32 in the epilogue, so a small gamma is never folded into the 16-bit weight.  Linear A-mode, act NONE, fp16 or fp32 R and C only;
+   * tb_gemm returns -22 for it with a conv gather, any act (LN_FWD / LN_BWD included), rowbias, C2, rs_out / rs_in or split_out, and
+   * tb_gemm_f32 / tb_gemm_f32_t return -22 for it always.  NULL: every launch computes what it computed without the field. */
+  const float* col_scale;
 } tb_gemm_desc;
 
 int tb_gemm(const tb_gemm_desc* d, tb_stream_t stream);

@@ -45,6 +45,7 @@ class GemmDesc(C.Structure):
         ("sync", C.c_void_p), ("sync_count", C.c_int64),
         ("split_out", C.POINTER(C.c_int32)),
         ("rs_out", C.c_void_p), ("rs_in", C.c_void_p), ("rs_ld", C.c_int64), ("rs_n", C.c_int32),
+        ("col_scale", C.c_void_p),
     ]
 
 

@@ -218,6 +218,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const tb_gemm_desc p, con
 
 int check_gemm_f32(const tb_gemm_desc& d, const GemmExt& x) {
   if (!d.A || !d.W || !d.C || d.M <= 0 || d.N <= 0 || d.K <= 0) return TB_EINVAL;
+  if (d.col_scale) return TB_EINVAL;   // LayerScale lives in the 16-bit path's epilogues only
   if (d.c_dtype != TB_F32 || (d.R && d.r_dtype != TB_F32)) return TB_EINVAL;
   if ((d.A2 == nullptr) != (d.W2 == nullptr)) return TB_EINVAL;
   if (d.A2 && (d.K1 <= 0 || d.K1 >= d.K || d.K1 % 4 || x.a_trans || x.w_trans || d.a_mode != TB_A_LINEAR)) return TB_EINVAL;

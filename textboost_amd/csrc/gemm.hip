@@ -148,7 +148,7 @@ __device__ __forceinline__ void tile_epilogue(const tb_gemm_desc& p, f32x16 (&ac
   const bool rb_uniform = !p.rowbias || (m_first / p.rows_per_group == m_last / p.rows_per_group);
   const bool act_gelu = p.act == TB_ACT_QUICK_GELU || p.act == TB_ACT_GELU;                 // C2 (optional) receives the fp16 pre-activation
   const bool act_grad = p.act == TB_ACT_QUICK_GELU_GRAD || p.act == TB_ACT_GELU_GRAD;       // C2 holds the saved pre-activation
-  const bool fast = lean_ok && S == 1 && (p.N % 8 == 0) && ef.c_vec && (!p.R || ef.r_vec) && rb_uniform &&
+  const bool fast = lean_ok && S == 1 && (p.N % 8 == 0) && ef.c_vec && (!p.R || ef.r_vec) && rb_uniform && !p.col_scale &&
                     ((p.act == TB_ACT_NONE || p.act == TB_ACT_SILU) ? !p.C2 : ((act_gelu && (!p.C2 || ef.c2_vec)) || (act_grad && ef.c2_vec)));
   const float alpha = p.alpha;
   const bool silu = p.act == TB_ACT_SILU, c_f32 = p.c_dtype == TB_F32, r_f32 = p.r_dtype == TB_F32;
@@ -1262,6 +1262,11 @@ extern "C" int tb_gemm(const tb_gemm_desc* dp, tb_stream_t stream) {
   if ((d.act == TB_ACT_QUICK_GELU_GRAD || d.act == TB_ACT_GELU_GRAD || d.act == TB_ACT_GEGLU_GRAD) && !d.C2) return TB_EINVAL;
   if (d.act == TB_ACT_GEGLU_GRAD && (d.N % 32 || d.c_dtype != TB_F16)) return TB_EINVAL;
   if (d.act < 0 || d.act > TB_ACT_LN_BWD) return TB_EINVAL;
+  // col_scale: the plain Linear epilogue only.  epilogue8 applies it, so every kernel below takes it through that path: gemm_kernel and gemm8_kernel
+  // leave their lean store paths to epilogue8 for it, the split-K reducers use it anyway, and tb_lin320_try declines such launches
+  if (d.col_scale && (d.a_mode != TB_A_LINEAR || d.act != TB_ACT_NONE || d.rowbias || d.C2 || d.rs_out || d.rs_in || d.split_out ||
+                      (d.c_dtype != TB_F16 && d.c_dtype != TB_F32) || (d.R && d.r_dtype != TB_F16 && d.r_dtype != TB_F32)))
+    return TB_EINVAL;
   if (d.a_mode == TB_A_CONV3X3 && (d.upsample == 2 || d.upsample == 3)) {
     // sub-pixel form of nearest-x2 + conv3x3 (gemm8.hip): upsample == 2 forward (A coarse [B, Hin, Win, Cin], C fine [B, 2 Hin, 2 Win, N],
     // W [4 classes][N][4 taps][Cin], K = 4 Cin), upsample == 3 dgrad (A fine [B, Hin, Win, Cin], C coarse [B, Hin / 2, Win / 2, N], W [N][16 Cin])

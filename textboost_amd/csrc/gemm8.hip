@@ -979,7 +979,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
     const int64_t m_last = CONV ? m0 + ((int64_t)(R - 1) * W + TW - 1) : m0 + BM - 1;
     const bool rb_uniform = rb_is_uniform(m_last);
     fast = p.c_dtype == TB_F16 && ef.c_vec && (!p.R || (ef.r_vec && p.r_dtype == TB_F16)) && (p.act == TB_ACT_NONE || p.act == TB_ACT_SILU) &&
-           !p.C2 && rb_uniform;
+           !p.C2 && rb_uniform && !p.col_scale;   // (LayerScale: the generic path's epilogue8 applies it)
     if (CONV) epi_load_bias8(p, n, b8);
   }
   // GEGLU forward (ff.net.0.proj, packed [h32 | g32] column blocks): unit = (row, 8 gate outputs); stores the fp16 projections (C2, for the

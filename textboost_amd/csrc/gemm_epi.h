@@ -34,6 +34,7 @@ __device__ __forceinline__ void glds16_asm_so(const void* sbase, uint32_t voff, 
 
 // Epilogue for 8 consecutive output columns n..n+7 of row m (shared by the MFMA kernel and the split-K reducer):
 // v = alpha*acc + bias + rowbias + R ; activation ; store C (fp16 | fp32), optionally C2 (pre-activation).
+// With col_scale (host-checked: act NONE, no rowbias): v = col_scale * (alpha*acc + bias) + R.
 // All global accesses are 16-byte vectors when the row pitch / base alignment allow (EpiFlags), else scalar.
 struct EpiFlags {
   bool c_vec, r_vec, c2_vec;
@@ -111,10 +112,18 @@ __device__ __forceinline__ void epilogue8(const tb_gemm_desc& p, const EpiFlags&
                                           const float* r, const f16x8& aux) {
   const bool full = n + 7 < p.N;
   const float* rb = p.rowbias ? p.rowbias + (m / p.rows_per_group) * p.ldrb : nullptr;
+  if (p.col_scale) {
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    v[e] = v[e] * p.alpha + bias8[e] + r[e];
-    if (rb && (full || n + e < p.N)) v[e] += rb[n + e];
+    for (int e = 0; e < 8; ++e) {
+      const float cs = (full || n + e < p.N) ? p.col_scale[n + e] : 0.f;
+      v[e] = (v[e] * p.alpha + bias8[e]) * cs + r[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      v[e] = v[e] * p.alpha + bias8[e] + r[e];
+      if (rb && (full || n + e < p.N)) v[e] += rb[n + e];
+    }
   }
   if (p.act == TB_ACT_QUICK_GELU) {
     f16x8 pre;

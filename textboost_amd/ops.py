@@ -180,7 +180,7 @@ DEFER_SPLITK = os.environ.get("TB_DEFER_SPLITK", "1") == "1"   # A/B switch: 0 =
 
 
 def gemm(A, W, out, *, K=None, A2=None, W2=None, bias=None, rowbias=None, rows_per_group=0, R=None, act=L.ACT_NONE,
-         alpha=1.0, C2=None, conv=None, ln_fwd=None, ln_bwd=None, defer=False, rs_out=None, lnfold=None, rs_slots=None):
+         alpha=1.0, C2=None, conv=None, ln_fwd=None, ln_bwd=None, defer=False, rs_out=None, lnfold=None, rs_slots=None, col_scale=None):
     """out[M,N] = A[M,K] @ W[N,K]^T (+epilogue). A/out/R may be column-slices of wider buffers (stride(0) = ld).
     conv = dict(B,Hin,Win,Cin,Hout,Wout,stride,sign,upsample,transposed) switches A to an NHWC 3x3 gather.
     ln_fwd = (gamma, beta, stats_out, y_out, eps): LayerNorm of the output row fused into the epilogue (only where `gemm_ln_ok`): `out` gets the
@@ -190,8 +190,12 @@ def gemm(A, W, out, *, K=None, A2=None, W2=None, bias=None, rowbias=None, rows_p
     rs_out = fp32 [M, slots, 2]: the launch also writes per-column-tile (sum, sum of squares) of its fp16 output rows (`lnfold_slots`);
     rs_slots = the number of slots per row the consumer is going to sum (checked against the tile the launch takes).
     lnfold = (rs, n_slots, c1, stats_out_or_None, eps): W is a `fold_layernorm` weight, A the RAW LayerNorm input, bias = c2; the LayerNorm is
-    applied as two per-row scalars in the epilogue (act NONE or GEGLU); stats_out [M, 2] receives (mean, rstd) for the backward."""
+    applied as two per-row scalars in the epilogue (act NONE or GEGLU); stats_out [M, 2] receives (mean, rstd) for the backward.
+    col_scale = fp32 [N]: out = col_scale * (alpha A W^T + bias) + R, in fp32 (DINOv2's LayerScale; plain Linear, act NONE only)."""
     d = L.GemmDesc()
+    if col_scale is not None:
+        assert col_scale.dtype == torch.float32 and col_scale.is_contiguous() and col_scale.numel() == W.shape[0]
+        d.col_scale = L.ptr(col_scale)
     if rs_out is not None:
         assert rs_out.dtype == torch.float32 and rs_out.is_contiguous() and rs_out.shape[0] == out.shape[0] and rs_out.shape[2] == 2
         d.rs_out, d.rs_ld = L.ptr(rs_out), rs_out.shape[1]
