@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- TextBoost train steps/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                                                           N > 1: this process launches N ranks itself (torch.distributed.run on 127.0.0.1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
                                                           (an existing launch: ranks from RANK / LOCAL_RANK / WORLD_SIZE; N must match)
@@ -9,7 +9,11 @@
 A "step" is one full optimizer step of train_textboost.py:1040-1149 on synthetic 4x64x64 latents: text-encoder
 LoRA fwd, frozen SD1.5 UNet fwd + dgrad bwd, MSE + KPL (teacher fwd + student fwd), text-encoder bwd, all-reduce of
 the trainable gradients (N>1), GradScaler/clip/AdamW/renorm -- captured in a HIP graph, inputs resident in HBM.
-Rank 0 prints ONE JSON line (fields per the driver contract, plus `roofline` and `cpu_baseline`)."""
+Rank 0 prints ONE JSON line (fields per the driver contract).
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, the --dump-outputs arrays, the line itself
+(`roofline` and `cpu_baseline` are null in it).  --full adds, after the timed steps and the dump, every measurement that takes a run of its
+own: the eager per-kernel roofline leg, the sustained-MFMA-rate and tile-clock probes, the quoted counter tables, the CPU baseline."""
 import argparse
 import json
 import os
@@ -447,8 +451,12 @@ def main():
     ap.add_argument("--precision", choices=["fp16", "fp32", "bf16"], default="fp16",
                     help="fp16 = --mixed_precision fp16, the reference driver's mode and the BASELINE.json metric; fp32 = the reference's default "
                          "no-AMP mode (README command; exact-fp32 MFMA at 1/16 of the fp16 matrix rate) -- a secondary measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements and fill `roofline` (one eager step under HIP events, "
+                         "the sustained-MFMA-rate and tile-clock probes, the committed counter tables) and `cpu_baseline` (the fp32 oracle "
+                         "on the host cores, minutes); without it a run only sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline leg and its probes out")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (scalars, updated trainable parameters, gradient, "
@@ -529,13 +537,13 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     sc = step.scalars()
-    if rank == 0 and args.dump_outputs:  # before the roofline leg: its extra eager step changes the parameters
+    if rank == 0 and args.dump_outputs:  # before the roofline leg of --full: its extra eager step changes the parameters
         dump_outputs(step, sc, args.dump_outputs)
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof, _ = roofline_leg(step)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not sd21 and not args.vae and args.precision == "fp16":  # the CPU baseline is the headline workload's
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not sd21 and not args.vae and args.precision == "fp16":  # the CPU baseline is the headline workload's
         try:
             cpu = cpu_baseline_leg()
         except Exception as e:  # the baseline is a reported reference, never fatal to the GPU number
@@ -569,12 +577,12 @@ def main():
         if args.precision == "fp32":
             metric = metric[:-1] + ", fp32 no-AMP mode)"
             workload += "; fp32 (no mixed precision) mode: every weight / activation / gradient fp32, v_mfma_f32_32x32x2_f32, no GradScaler"
-        if sd21:  # secondary measurement; algorithmic FLOP taken from the recorded launches of the eager leg
+        if sd21:  # secondary measurement; algorithmic FLOP taken from the recorded launches of the eager leg (--full)
             metric = "train steps/sec (batch=%d, SD2.1 shapes, %d^2 latents, LoRA r=8)" % (args.batch, args.latent)
             workload = ("SURVEY 8(d) config 4: SD2.x UNet (865.9M, Linear proj_in/out, head dim 64) + OpenCLIP-H text encoder (23 layers, "
                         "D=1024) LoRA r=8 + KPL teacher, per-GPU batch %d, %dx%d latents; random-init weights; one HIP graph"
                         % (args.batch, args.latent, args.latent))
-            flop_per_image = (roof["recorded_matmul_tflop_per_step"] * 1e12 / args.batch) if roof else float("nan")
+            flop_per_image = (roof["recorded_matmul_tflop_per_step"] * 1e12 / args.batch) if roof else None
         out = {
             # whole-job aggregate: every rank runs a per-GPU-batch step (weak scaling), so the job does `world` of the metric's batch-8 steps per
             # global step; sps is the rate of the slowest rank (the timed region ends at a barrier, dt is the max over ranks)
@@ -584,8 +592,8 @@ def main():
             "config": {"workload": workload,
                        "per_gpu_batch": args.batch, "global_batch": args.batch * world, "parallelism": f"dp{world}",
                        "images_per_s": round(sps * args.batch * world, 2)},
-            "alg_tflops_per_gpu": round(sps * args.batch * flop_per_image / 1e12, 2),
-            "frac_of_mfma_peak_whole_step": round(sps * args.batch * flop_per_image / 1e12 / MFMA_PEAK_TFLOPS, 4),
+            "alg_tflops_per_gpu": None if flop_per_image is None else round(sps * args.batch * flop_per_image / 1e12, 2),
+            "frac_of_mfma_peak_whole_step": None if flop_per_image is None else round(sps * args.batch * flop_per_image / 1e12 / MFMA_PEAK_TFLOPS, 4),
             "loss": sc["loss"], "loss_scale": sc["loss_scale"], "found_inf_last": sc["found_inf"], "opt_steps": sc["opt_steps"],
             "graph_mode": "eager" if args.no_graph else step.graph_mode,  # "single" | "single+rccl" (all-reduce inside the step graph) | "two+eager-rccl"
             "rccl_world_size": n_ranks if dist is not None else None,

@@ -1,27 +1,28 @@
 #!/bin/bash
-# usage (GPU box): scratch/refresh_profiles_r2.sh -> gpurun_out/r02/: kernel-trace stats of the bench command, FETCH/WRITE PMC passes, LDS / issue counters
+# usage (GPU box): scratch/refresh_profiles_r2.sh -> $OUT/r02/: kernel-trace stats of the bench command, FETCH/WRITE PMC passes, LDS / issue counters
+OUT=${OUT:?set OUT to the absolute path of the directory that takes the results}
 R=$GRAFT_REPO_ROOT
-cd $R; mkdir -p gpurun_out/r02
+cd $R; mkdir -p $OUT/r02
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $R/gpurun_out/r02/trace -o r02 -- python $R/bench.py --steps 10 --warmup 5 --no-cpu-baseline > $R/gpurun_out/r02/trace.log 2>&1
-grep '^{"metric"' $R/gpurun_out/r02/trace.log | tail -1 > $R/gpurun_out/r02/trace_bench_line.json
-f=$(ls $R/gpurun_out/r02/trace/*.db 2>/dev/null | head -1); [ -z "$f" ] && f=$(ls $R/gpurun_out/r02/trace/*/*.db | head -1)
-python $R/scratch/rocpd_stats.py $f 70 > $R/gpurun_out/r02/kernel_stats.txt
-rm -rf $R/gpurun_out/r02/trace
+rocprofv3 --kernel-trace --stats -d $OUT/r02/trace -o r02 -- python $R/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $OUT/r02/trace.log 2>&1
+grep '^{"metric"' $OUT/r02/trace.log | tail -1 > $OUT/r02/trace_bench_line.json
+f=$(ls $OUT/r02/trace/*.db 2>/dev/null | head -1); [ -z "$f" ] && f=$(ls $OUT/r02/trace/*/*.db | head -1)
+python $R/scratch/rocpd_stats.py $f 70 > $OUT/r02/kernel_stats.txt
+rm -rf $OUT/r02/trace
 for set in "FETCH_SIZE" "WRITE_SIZE"; do
-  rocprofv3 --kernel-trace --pmc $set -d $R/gpurun_out/r02/pmc_traffic -o $set --output-format csv -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $R/gpurun_out/r02/pmc_$set.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set -d $OUT/r02/pmc_traffic -o $set --output-format csv -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $OUT/r02/pmc_$set.log 2>&1
 done
-python $R/scratch/pmc_traffic.py $R/gpurun_out/r02/pmc_traffic $R/gpurun_out/r02/pmc_traffic.json > $R/gpurun_out/r02/pmc_traffic_top.txt
+python $R/scratch/pmc_traffic.py $OUT/r02/pmc_traffic $OUT/r02/pmc_traffic.json > $OUT/r02/pmc_traffic_top.txt
 i=0
 for set in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_SALU" \
            "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU_TRANS_F32"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set -d $R/gpurun_out/r02/pmc_sq -o p$i --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $R/gpurun_out/r02/pmc_sq$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set -d $OUT/r02/pmc_sq -o p$i --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $OUT/r02/pmc_sq$i.log 2>&1
 done
-python - <<PY > $R/gpurun_out/r02/pmc_sq.txt
+python - <<PY > $OUT/r02/pmc_sq.txt
 import csv, glob, collections, re
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
-for f in glob.glob("$R/gpurun_out/r02/pmc_sq/*counter_collection.csv"):
+for f in glob.glob("$OUT/r02/pmc_sq/*counter_collection.csv"):
     for r in csv.DictReader(open(f)):
         k = re.sub(r"\(anonymous namespace\)::|^void ", "", r["Kernel_Name"]).split("(")[0][:70]
         if any(x in k for x in ("gemm", "conv_halo", "attn_")):
@@ -33,5 +34,5 @@ for k, c in sorted(agg.items(), key=lambda kv: -sum(kv[1].get("SQ_WAVE_CYCLES", 
     for name, v in sorted(c.items()): print(f"   {name:30s} {sum(v)/len(v):16.0f}")
     if "SQ_VALU_MFMA_BUSY_CYCLES" in c and "SQ_WAVE_CYCLES" in c: pass
 PY
-rm -rf $R/gpurun_out/r02/pmc_sq $R/gpurun_out/r02/pmc_traffic
-ls -la $R/gpurun_out/r02
+rm -rf $OUT/r02/pmc_sq $OUT/r02/pmc_traffic
+ls -la $OUT/r02

@@ -1,28 +1,29 @@
 #!/bin/bash
-# usage (GPU box): scratch/refresh_profiles_r3.sh -> gpurun_out/r05/: kernel-trace stats of the bench command, FETCH / WRITE PMC passes, SQ counters
+# usage (GPU box): scratch/refresh_profiles_r3.sh -> $OUT/r05/: kernel-trace stats of the bench command, FETCH / WRITE PMC passes, SQ counters
+OUT=${OUT:?set OUT to the absolute path of the directory that takes the results}
 R=$GRAFT_REPO_ROOT
-cd $R; mkdir -p gpurun_out/r05
+cd $R; mkdir -p $OUT/r05
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $R/gpurun_out/r05/trace -o r05 -- python $R/bench.py --steps 10 --warmup 5 --no-cpu-baseline > $R/gpurun_out/r05/trace.log 2>&1
-grep '^{"metric"' $R/gpurun_out/r05/trace.log | tail -1 > $R/gpurun_out/r05/trace_bench_line.json
-f=$(ls $R/gpurun_out/r05/trace/*.db 2>/dev/null | head -1); [ -z "$f" ] && f=$(ls $R/gpurun_out/r05/trace/*/*.db | head -1)
-python $R/scratch/rocpd_stats.py $f 80 > $R/gpurun_out/r05/kernel_stats.txt
-python $R/scratch/step_timeline.py $f $R/gpurun_out/r05/step_timeline.txt
-rm -rf $R/gpurun_out/r05/trace
+rocprofv3 --kernel-trace --stats -d $OUT/r05/trace -o r05 -- python $R/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline > $OUT/r05/trace.log 2>&1
+grep '^{"metric"' $OUT/r05/trace.log | tail -1 > $OUT/r05/trace_bench_line.json
+f=$(ls $OUT/r05/trace/*.db 2>/dev/null | head -1); [ -z "$f" ] && f=$(ls $OUT/r05/trace/*/*.db | head -1)
+python $R/scratch/rocpd_stats.py $f 80 > $OUT/r05/kernel_stats.txt
+python $R/scratch/step_timeline.py $f $OUT/r05/step_timeline.txt
+rm -rf $OUT/r05/trace
 for set in "FETCH_SIZE" "WRITE_SIZE"; do
-  rocprofv3 --kernel-trace --pmc $set -d $R/gpurun_out/r05/pmc_traffic -o $set --output-format csv -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $R/gpurun_out/r05/pmc_$set.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set -d $OUT/r05/pmc_traffic -o $set --output-format csv -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $OUT/r05/pmc_$set.log 2>&1
 done
-python $R/scratch/pmc_traffic.py $R/gpurun_out/r05/pmc_traffic $R/gpurun_out/r05/pmc_traffic.json > $R/gpurun_out/r05/pmc_traffic_top.txt
+python $R/scratch/pmc_traffic.py $OUT/r05/pmc_traffic $OUT/r05/pmc_traffic.json > $OUT/r05/pmc_traffic_top.txt
 i=0
 for set in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_SALU" \
            "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU_TRANS_F32"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set -d $R/gpurun_out/r05/pmc_sq -o p$i --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $R/gpurun_out/r05/pmc_sq$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set -d $OUT/r05/pmc_sq -o p$i --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-graph > $OUT/r05/pmc_sq$i.log 2>&1
 done
-python - <<PY > $R/gpurun_out/r05/pmc_sq.txt
+python - <<PY > $OUT/r05/pmc_sq.txt
 import csv, glob, collections, re
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
-for f in glob.glob("$R/gpurun_out/r05/pmc_sq/*counter_collection.csv"):
+for f in glob.glob("$OUT/r05/pmc_sq/*counter_collection.csv"):
     for r in csv.DictReader(open(f)):
         k = re.sub(r"\(anonymous namespace\)::|^void ", "", r["Kernel_Name"]).split("(")[0][:70]
         if any(x in k for x in ("gemm", "conv_halo", "attn_", "ff_fused")):
@@ -35,6 +36,6 @@ for k, c in sorted(agg.items(), key=lambda kv: -sum(kv[1].get("SQ_WAVE_CYCLES", 
     print(f"{k}  (x{n})")
     for name, v in sorted(c.items()): print(f"   {name:30s} {sum(v)/len(v):16.0f}")
 PY
-python $R/scratch/mfma_busy.py $R/gpurun_out/r05/pmc_sq.txt $R/gpurun_out/r05/mfma_busy.json > $R/gpurun_out/r05/mfma_busy.txt
-rm -rf $R/gpurun_out/r05/pmc_sq $R/gpurun_out/r05/pmc_traffic
-ls -la $R/gpurun_out/r05
+python $R/scratch/mfma_busy.py $OUT/r05/pmc_sq.txt $OUT/r05/mfma_busy.json > $OUT/r05/mfma_busy.txt
+rm -rf $OUT/r05/pmc_sq $OUT/r05/pmc_traffic
+ls -la $OUT/r05
