@@ -1,22 +1,31 @@
 #!/usr/bin/env python3
-"""CLIP-T / CLIP-I / DINO evaluation of generated DreamBooth images: the reference's eval_dreambooth.py (`clip_score` :353-374, `clip_i`
-:377-453, `dino_score` :456-543, the CSV of `main` :568-628) with the same flags, on the HIP CLIP ViT-L/14 of textboost_amd/clip_score.py and
-the HIP DINOv2 ViT-L/14 of textboost_amd/dino_score.py.
+"""Image generation and CLIP-T / CLIP-I / DINO evaluation of a trained DreamBooth run: the reference's eval_dreambooth.py (`generate` :270-350,
+`clip_score` :353-374, `clip_i` :377-453, `dino_score` :456-543, the CSV of `main` :568-628) with the same flags, on the HIP executors of
+textboost_amd/generate.py (text encoder with the trained adapter and tokens, guided DPM-Solver++ sampling, VAE decoder), the HIP CLIP ViT-L/14
+of textboost_amd/clip_score.py and the HIP DINOv2 ViT-L/14 of textboost_amd/dino_score.py.
 
+    python eval_dreambooth.py <path> --model <diffusers model dir> --metric clip-t clip-i dino --clip-model <CLIPModel dir> \
+        --dino-model <DINOv2 weights> [--instances dog can ...] [--token-format "<INSTANCE> SUBJECT"] [--prompt-batch 16]
     python eval_dreambooth.py <path> --skip-gen --metric clip-t clip-i dino --clip-model <CLIPModel dir> --dino-model <DINOv2 weights> \
         [--outdir ./benchmarks] [--seeds 0 1 2 3] [--train-dir ...] [--val-dir ...] [--dreambooth-path ./data/dreambooth] [--checkpoint N]
         [--output-desc D]
 
-Images are read from `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/*.png` (the reference's `generate()` with
---skip-gen); the scores go to `<path>/metric{_ckpt<N>|_last}{_<desc>}.csv` in the reference's format.  --clip-model names a local transformers
+Without --skip-gen the images are generated first: for every subject (`--instances`, else those of the 30 DreamBooth subjects that exist as
+sub-directories of `path`) the trained output directory `<path>/<instance>[/checkpoint-<N>]` is read back (text_encoder/ adapter, `<token>.bin`),
+and 25 prompts x `--seeds` are sampled (25 steps, guidance 7.5, one latent per seed) into
+`<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/<prompt>.png`.  --model names a LOCAL diffusers model directory (unet/,
+vae/, text_encoder/, tokenizer/, scheduler/); the reference's aliases (sd15, ...) name hub repositories and are refused.  The scores are then
+computed from the PNGs exactly as a --skip-gen run computes them.
+
+Images are read from `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/*.png`; the scores go to
+`<path>/metric{_ckpt<N>|_last}{_<desc>}.csv` in the reference's format.  --clip-model names a local transformers
 `CLIPModel` directory (config.json, model.safetensors, vocab.json, merges.txt): it replaces the reference's download of ViT-L/14@336px.
 --dino-model names the hub's `dinov2_vitl14_pretrain.pth` or a local transformers `Dinov2Model` directory: it replaces the reference's
 `torch.hub.load('facebookresearch/dinov2', 'dinov2_vitl14')`.  DINO reads the real images from `<dreambooth-path>/<instance>/*.*` (sorted) and
 takes N, the number of seen ones, from `path` as the reference does (`<name>-<model>-n<N>`, e.g. `out/tb-sd15-n1`): an instance's first N real
 images are seen, the rest unseen.
 
-Not built here: image generation (a run without --skip-gen) and the VQA score (FlanT5-XXL): asking for them is an error, so that a 0.000
-placeholder in the CSV never reads as a score."""
+Not built here: the VQA score (FlanT5-XXL): asking for it is an error, so that a 0.000 placeholder in the CSV never reads as a score."""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +56,8 @@ def build_parser():
     p.add_argument("--dreambooth-path", type=str, default="./data/dreambooth")
     p.add_argument("--train-dir", type=str, default="./data/dreambooth_n1_train")
     p.add_argument("--val-dir", type=str, default="./data/dreambooth_n1_val")
-    p.add_argument("--model", type=str, default=None)
+    p.add_argument("--model", type=str, default=None, help="local diffusers model directory (image generation only)")
+    p.add_argument("--prompt-batch", type=int, default=16, help="prompts per sampling batch at most (image generation only)")
     p.add_argument("--output-desc", type=str, default=None)
     p.add_argument("--clip-model", type=str, default=None, help="local transformers CLIPModel directory (ViT-L/14@336px) with its tokenizer files")
     p.add_argument("--dino-model", type=str, default=None,
@@ -59,8 +69,13 @@ def build_parser():
 def check_args(args):
     """the refusals, before anything touches the device"""
     if not args.skip_gen:
-        raise SystemExit("eval_dreambooth.py: image generation from a trained output directory is not built; generate the images elsewhere "
-                         "and pass --skip-gen")
+        if not args.model:
+            raise SystemExit("eval_dreambooth.py: generating the images needs --model DIR (a local diffusers model directory: unet/, vae/, "
+                             "text_encoder/, tokenizer/, scheduler/); pass --skip-gen to score images that exist already")
+        from textboost_amd.generate import check_model_dir
+        check_model_dir(args.model, "eval_dreambooth.py")
+        if args.prompt_batch <= 0:
+            raise SystemExit("eval_dreambooth.py: --prompt-batch must be positive")
     unknown = [m for m in args.metric if m not in BUILT_METRICS + ("vqa",)]
     if unknown:
         raise SystemExit(f"eval_dreambooth.py: unknown --metric {unknown}")
@@ -251,9 +266,23 @@ def evaluate(args, evaluator=None, dino_evaluator=None):
     return results
 
 
+def generate(args):
+    """eval_dreambooth.py `generate()` without --skip-gen: the PNGs under `image_root(args)`"""
+    from textboost_amd.generate import generate_run, select_instances
+    path = args.path.rstrip("/") or args.path
+    try:
+        instances = select_instances(path, args.instances)
+    except SystemExit as e:
+        raise SystemExit(f"eval_dreambooth.py: {e}") from None
+    return generate_run(path, args.model, instances, args.seeds, image_root(args), checkpoint=args.checkpoint, token_format=args.token_format,
+                        prompt_batch=args.prompt_batch)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_args(args)
+    if not args.skip_gen:
+        generate(args)
     return evaluate(args)
 
 

@@ -336,6 +336,10 @@ int tb_dpm_step(float* x, const void* eps2, float* m_prev, void* x2, int64_t n_p
                 float ca, float cb, float cc, tb_stream_t stream);
 /* (decoded / 2 + 0.5).clamp(0, 1): NHWC fp32 [B*HW, ld >= C] -> NCHW fp32 [B, C, HW] */
 int tb_vae_image(const float* decoded, int64_t ld, float* image, int B, int HW, int C, tb_stream_t stream);
+/* the same decoder output as bytes: decoded fp32 [B*HW, ld >= 3] (R, G, B in the first three columns) -> image u32 [B*HW] in the resident RGBX
+   format of tb_img_pack_rgb (R | G << 8 | B << 16, X = 0).  Per channel uint8(rint(clamp(x / 2 + 0.5, 0, 1) * 255)), fp32, round half to even;
+   NaN -> 0. */
+int tb_vae_image_rgbx(const float* decoded, int64_t ld, uint32_t* image, int B, int HW, tb_stream_t stream);
 /* F.mse_loss(pred.float(), target.float()).mean() (:1085-1090); dpred = loss_scale[0] * dloss/dpred (fp32) */
 int tb_mse_loss(const void* pred, const float* target, float* dpred, float* loss_out, const float* loss_scale, int64_t N,
                 float* ws /* >= 128 floats of scratch for the two-stage reduction, or NULL: one block */, tb_stream_t stream);

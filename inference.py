@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Images of one prompt from a trained output directory: the reference's inference.py with its flags, on the HIP executors of
+textboost_amd/generate.py.
+
+    python inference.py <output_dir> --model <diffusers model dir> --prompt "photo of a <dog> dog" [--seeds 0 1 2 3] [--output grid.jpg]
+        [--checkpoint N]
+
+`<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`); the text encoder is the plain CLIP text model
+(no null-embedding pins: the reference's pipeline here holds a `CLIPTextModel`, inference.py:47-52), one latent PER SEED, the pipeline's default
+50 steps at guidance 7.5 with DPM-Solver++.  With --output the images form one grid (1 x len(seeds)); without it each is written to
+`<prompt with _ for spaces>_<seed>.jpg` in the working directory.
+
+Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
+reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
+latent of a seed is drawn on the CPU (textboost_amd.generate.seeded_latent), the same on every machine."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("path", type=str, help="path to model")
+    p.add_argument("--model", type=str, default=None, help="local diffusers model directory")
+    p.add_argument("--prompt", type=str, default="photo of a <dog> dog")
+    p.add_argument("--outdir", type=str, default="./benchmarks")
+    p.add_argument("--checkpoint", type=int, default=None)
+    p.add_argument("--skip-gen", action="store_true")
+    p.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
+    p.add_argument("--output", type=str, default=None)
+    p.add_argument("--steps", type=int, default=50, help="sampling steps (the pipeline's default)")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from textboost_amd import generate as G
+    if not args.model:
+        raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
+    G.check_model_dir(args.model, "inference.py")
+    path = args.path.rstrip("/") or args.path
+    if args.checkpoint is not None:
+        path = os.path.join(path, f"checkpoint-{args.checkpoint}")
+    run = G.read_run_dir(path)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("inference.py needs an MI355X: the product path has no CPU fallback")
+    from textboost_amd import augment
+    n = len(args.seeds)
+    with torch.no_grad():
+        pipe = G.Pipeline.from_model_dir(args.model, n, steps=args.steps, guidance=7.5)
+        base = G.load_base_text(args.model)
+        te, tokenizer = G.load_text_encoder(args.model, run, 2 * n, base=base)
+        T = base.geo.max_pos
+        ids = G.tokenize(tokenizer, [""] * n + [args.prompt] * n, T).to(pipe.dev)
+        states = te.forward(ids, pins=False).view(2, n * T, -1)
+        latents = torch.cat([G.seeded_latent(s, pipe.size) for s in args.seeds]).to(pipe.dev)
+        rgbx = pipe.images(states[1], states[0], latents, what=f"prompt {args.prompt!r}, seeds {args.seeds}")
+        from PIL import Image
+        images = [Image.fromarray(augment.to_host_rgb(rgbx[k])) for k in range(n)]
+    if args.output is not None:
+        grid = Image.new("RGB", (n * images[0].width, images[0].height))     # diffusers.utils.make_image_grid(images, 1, n)
+        for k, im in enumerate(images):
+            grid.paste(im, box=(k * im.width, 0))
+        grid.save(args.output)
+        print(f"wrote {args.output}")
+    else:
+        for seed, im in zip(args.seeds, images):
+            out = args.prompt.replace(" ", "_") + f"_{seed}.jpg"
+            im.save(out)
+            print(f"wrote {out}")
+
+
+if __name__ == "__main__":
+    main()

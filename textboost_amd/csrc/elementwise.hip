@@ -618,6 +618,29 @@ __global__ __launch_bounds__(256) void vae_image_kernel(const float* __restrict_
   out[idx] = fminf(fmaxf(v, 0.f), 1.f);
 }
 
+// decoder output -> resident RGBX image (the format of tb_img_pack_rgb: R | G << 8 | B << 16, X = 0), one pixel per lane.  Per channel
+// uint8(rint(clamp(x / 2 + 0.5, 0, 1) * 255)): x / 2 is exact, so the fma rounds once like the two torch ops; the product with 255 is rounded on
+// its own before rint (half-way cases would flip otherwise); NaN -> 0.  VEC: ld == 4 and a 16-byte aligned base, one dwordx4 load per pixel.
+__device__ __forceinline__ uint32_t image_byte(float x) {
+  const float v = fmaf(x, 0.5f, 0.5f);
+  const float c = v > 0.f ? fminf(v, 1.f) : 0.f;   // NaN compares false
+  return (uint32_t)rintf(__fmul_rn(c, 255.f));
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void vae_image_rgbx_kernel(const float* __restrict__ in, int64_t ld, uint32_t* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over B * HW pixels
+  if (i >= n) return;
+  float r, g, b;
+  if (VEC) {
+    const float4 v = reinterpret_cast<const float4*>(in)[i];
+    r = v.x, g = v.y, b = v.z;
+  } else {
+    const float* p = in + i * ld;
+    r = p[0], g = p[1], b = p[2];
+  }
+  out[i] = image_byte(r) | (image_byte(g) << 8) | (image_byte(b) << 16);
+}
+
 }  // namespace
 
 static int g_boundary_mfma = 1;   // tb_boundary_conv_set_variant: 1 = the matrix-core boundary convolutions (round 5), 0 = the VALU kernels
@@ -870,6 +893,18 @@ extern "C" int tb_vae_image(const float* decoded, int64_t ld, float* image, int 
   (void)hipGetLastError();  // drop any stale (non-sticky) error left by an earlier runtime call
   if (!decoded || !image || B <= 0 || HW <= 0 || C <= 0 || ld < C) return TB_EINVAL;
   hipLaunchKernelGGL(vae_image_kernel, GRID1D((int64_t)B * C * HW), dim3(256), 0, (hipStream_t)stream, decoded, ld, image, B, HW, C);
+  TB_CHECK_LAUNCH();
+  return TB_OK;
+}
+
+extern "C" int tb_vae_image_rgbx(const float* decoded, int64_t ld, uint32_t* image, int B, int HW, tb_stream_t stream) {
+  (void)hipGetLastError();  // drop any stale (non-sticky) error left by an earlier runtime call
+  if (!decoded || !image || B <= 0 || HW <= 0 || ld < 3) return TB_EINVAL;
+  const int64_t n = (int64_t)B * HW;
+  if (ld == 4 && ((uintptr_t)decoded & 15) == 0)
+    hipLaunchKernelGGL(vae_image_rgbx_kernel<true>, GRID1D(n), dim3(256), 0, (hipStream_t)stream, decoded, ld, image, n);
+  else
+    hipLaunchKernelGGL(vae_image_rgbx_kernel<false>, GRID1D(n), dim3(256), 0, (hipStream_t)stream, decoded, ld, image, n);
   TB_CHECK_LAUNCH();
   return TB_OK;
 }

@@ -1,0 +1,395 @@
+"""Images from a trained output directory: the read side of the layout `checkpoint.py` writes, and the generation protocol of the reference's
+eval_dreambooth.py (`load_pipeline` :175-215, `generate_from_pipeline` :218-267, `generate` :270-350) and inference.py (:47-112).
+
+    read_run_dir(<path>/<instance>[/checkpoint-N]) -> TrainedRun      text_encoder/adapter_config.json + adapter_model.safetensors, <token>.bin
+    load_text_encoder(model_dir, run, ...)      -> HipTextEncoder (+ tokenizer) with the adapter, the learned rows and the null-embedding pins
+    Pipeline.from_model_dir(model_dir, ...)     -> UNet, VAE decoder and sampler executors, built once per run
+    generate_instance(pipe, base, run, ...)     -> <outdir>/seed<s>/<instance>/<prompt>.png for every seed, 25 prompts each
+
+Device work: `HipTextEncoder.forward`, `HipSampler.denoise` (guided DPM-Solver++ steps on `HipUNet.forward`), `HipVAEDecoder.decode_rgbx`
+(`tb_vae_image_rgbx`: decoder output -> resident RGBX bytes).  One download per prompt batch; PNG encoding runs on host threads beside the
+next batch.
+
+Stated deviations from the reference:
+  * seeding: the reference seeds a `torch.Generator` and never uses it (:236-240), so its images differ from run to run.  Here the latent of a
+    seed is `torch.randn(1, 4, size, size, generator=torch.Generator().manual_seed(seed))` on the CPU in fp32, rounded to fp16 (the reference
+    draws in its pipeline's fp16): the same on every machine.
+  * the 25 prompts run as even batches of at most `prompt_batch` (16: 13 + 12) on ONE set of executors sized for the larger batch; the short
+    batch is padded with its last prompt and the padding image is dropped.  The reference runs 16 + 9.
+  * the null embedding is the training-time one (the base encoder's output for the empty prompt, or the shipped SD2.1-base tensor); the reference
+    loads `assets/start_emb_<model>.pt`, a file it does not ship.
+  * `--model` is a local diffusers directory; UNet, decoder and sampler are built once per run and only the text encoder is reloaded per subject.
+"""
+from __future__ import annotations
+
+import json
+import os
+import time
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+HUB_ALIASES = ("sd14", "sd15", "sd21base", "sd21")     # eval_dreambooth.py:18-23 / inference.py:15-20: names of hub repositories
+SKIPPED_BIN = ("optimizer.bin", "scheduler.bin")       # :199-206
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj")
+MAX_PNG_THREADS = 8
+
+
+# ------------------------------------------------------------------------------------------------ subjects, prompts, names (host only)
+def load_eval_prompts() -> Tuple[Dict[str, str], List[str], List[str]]:
+    """(subject -> class name, the 25 object prompts, the 25 live-subject prompts) of eval_dreambooth.py:25-112"""
+    with open(os.path.join(_HERE, "eval_prompts.json")) as f:
+        d = json.load(f)
+    return dict(d["instances"]), list(d["object_prompts"]), list(d["live_prompts"])
+
+
+def is_live(instance: str) -> bool:
+    """:142-146"""
+    return load_eval_prompts()[0][instance] in ("cat", "dog")
+
+
+def prompt_templates(instance: str) -> List[str]:
+    instances, obj, live = load_eval_prompts()
+    if instance not in instances:
+        raise ValueError(f"Invalid instance: {instance}")   # :228
+    return live if instances[instance] in ("cat", "dog") else obj
+
+
+def identifier_for(token_format: str, instance: str, files: Sequence[str]) -> str:
+    """:329-337: INSTANCE -> the subject; one copy per placeholder vector (= files of the model path whose name starts with the subject's), every
+    '>' of copy i becoming '_i>'; then SUBJECT -> the class name."""
+    cls = load_eval_prompts()[0][instance]
+    num_vectors = len([f for f in files if f.startswith(instance)])
+    identifier = token_format.replace("INSTANCE", instance)
+    if num_vectors > 1:
+        identifier = " ".join(identifier.replace(">", f"_{i}>") for i in range(num_vectors))
+    return identifier.replace("SUBJECT", cls)
+
+
+def instance_prompts(instance: str, identifier: str) -> List[str]:
+    return [t.format(identifier) for t in prompt_templates(instance)]
+
+
+def image_filename(prompt: str, identifier: str, instance: str) -> str:
+    """:263"""
+    cls = load_eval_prompts()[0][instance]
+    return f"{prompt.replace(identifier, cls).replace(' ', '_')}.png"
+
+
+def prompt_batches(prompts: Sequence[str], prompt_batch: int) -> List[List[str]]:
+    """even batches of at most `prompt_batch`, in order (25, 16 -> 13 + 12)"""
+    n = len(prompts)
+    k = -(-n // prompt_batch)
+    base, rem = divmod(n, k)
+    out, off = [], 0
+    for i in range(k):
+        m = base + (1 if i < rem else 0)
+        out.append(list(prompts[off:off + m]))
+        off += m
+    return out
+
+
+def model_path_of(path: str, instance: str, checkpoint: Optional[int]) -> str:
+    """:318-319"""
+    return os.path.join(path, instance, f"checkpoint-{checkpoint}" if checkpoint is not None else "")
+
+
+def select_instances(path: str, requested: Optional[Sequence[str]]) -> List[str]:
+    """--instances (in the subject table's order, :271-275), else those of the 30 subjects that exist as sub-directories of `path`"""
+    table = load_eval_prompts()[0]
+    if requested is not None:
+        unknown = [i for i in requested if i not in table]
+        if unknown:
+            raise SystemExit(f"unknown --instances {unknown}: the subjects are {', '.join(table)}")
+        return [i for i in table if i in requested]
+    found = [i for i in table if os.path.isdir(os.path.join(path, i))]
+    if not found:
+        raise SystemExit(f"no trained subject under {path}: expected sub-directories named after the DreamBooth subjects ({', '.join(list(table)[:4])}, ...)")
+    return found
+
+
+def seeded_latent(seed: int, size: int) -> torch.Tensor:
+    """the one latent of a seed: CPU, fp32 draw, rounded to fp16 (returned as fp32 [1, 4, size, size])"""
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.randn(1, 4, size, size, generator=g, dtype=torch.float32).half().float()
+
+
+# ------------------------------------------------------------------------------------------------ reader of a trained output directory
+@dataclass
+class TrainedRun:
+    path: str
+    rank: int
+    lora: Dict[str, torch.Tensor]                       # peft adapter keys (checkpoint.lora_state_dict)
+    tokens: List[Tuple[str, torch.Tensor]] = field(default_factory=list)   # (name, fp32 [D]) in loading order
+    files: List[str] = field(default_factory=list)      # os.listdir(path): the identifier counts the subject's files
+
+
+def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedRun:
+    """`load_adapter(<path>/text_encoder)` + `load_textual_inversion` of every `*.bin` in sorted order except optimizer.bin / scheduler.bin
+    (:193-206).  What the HIP encoder cannot apply is refused by name.  hidden_size: the encoder's width when the caller knows it (otherwise
+    taken from the adapter's lora_A)."""
+    from safetensors.torch import load_file
+    te_dir = os.path.join(model_path, "text_encoder")
+    if not os.path.isdir(te_dir):
+        raise FileNotFoundError(f"{model_path}: no text_encoder/ directory (not a trained output directory)")
+    with open(os.path.join(te_dir, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    r = int(cfg.get("r", 0))
+    if cfg.get("use_dora"):
+        raise NotImplementedError(f"{te_dir}: use_dora adapters are not built")
+    if cfg.get("use_rslora"):
+        raise NotImplementedError(f"{te_dir}: use_rslora adapters are not built (scaling alpha / sqrt(r))")
+    if r and cfg.get("lora_alpha", r) != r:
+        raise NotImplementedError(f"{te_dir}: lora_alpha = {cfg.get('lora_alpha')} != r = {r}: the kernels carry no separate LoRA scaling")
+    targets = cfg.get("target_modules") or []
+    targets = [targets] if isinstance(targets, str) else list(targets)
+    if r and sorted(targets) != sorted(LORA_TARGETS):
+        raise NotImplementedError(f"{te_dir}: target_modules {sorted(targets)}: only q_proj / k_proj / v_proj adapters are built")
+    lora = load_file(os.path.join(te_dir, "adapter_model.safetensors")) if r else {}
+    if r:
+        a = [v for k, v in lora.items() if k.endswith("lora_A.weight")]
+        if not a or any(t.shape[0] != r for t in a):
+            raise ValueError(f"{te_dir}: adapter_model.safetensors does not hold rank-{r} lora_A tensors")
+        hidden_size = hidden_size or int(a[0].shape[1])
+    files = sorted(os.listdir(model_path))
+    tokens: List[Tuple[str, torch.Tensor]] = []
+    for name in files:
+        if not name.endswith(".bin") or name in SKIPPED_BIN:
+            continue
+        d = torch.load(os.path.join(model_path, name), map_location="cpu")
+        if not isinstance(d, dict) or len(d) != 1:
+            raise ValueError(f"{model_path}/{name}: expected a {{token: tensor}} dictionary with one entry")
+        (tok, t), = d.items()
+        t = t.detach().float()
+        if t.dim() == 1:
+            t = t[None]
+        if t.dim() != 2:
+            raise ValueError(f"{model_path}/{name}: token {tok!r} has shape {tuple(t.shape)}; expected [D], [1, D] or [n, D]")
+        if hidden_size is not None and t.shape[1] != hidden_size:
+            raise ValueError(f"{model_path}/{name}: token {tok!r} has width {t.shape[1]}, the text encoder's hidden_size is {hidden_size}")
+        names = [tok] + [f"{tok}_{i}" for i in range(1, t.shape[0])]    # diffusers load_textual_inversion: tok, tok_1, ..., tok_{n-1}
+        tokens += [(n, t[i].clone()) for i, n in enumerate(names)]
+    return TrainedRun(path=model_path, rank=r, lora=lora, tokens=tokens, files=files)
+
+
+# ------------------------------------------------------------------------------------------------ text encoder of one subject
+@dataclass
+class BaseText:
+    """what every subject of a run shares: the base encoder's weights and geometry and the null embedding"""
+    model_dir: str
+    geo: object
+    state_dict: Dict[str, torch.Tensor]
+    null: torch.Tensor
+
+
+def load_base_text(model_dir: str, device="cuda") -> BaseText:
+    from safetensors.torch import load_file
+    from . import models
+    from .text_encoder import HipTextEncoder
+    from .workload import BOS, EOS
+    wpath = os.path.join(model_dir, "text_encoder", "model.safetensors")
+    if not os.path.exists(wpath):
+        raise FileNotFoundError(f"{wpath} is missing: --model must be a local diffusers model directory")
+    with open(os.path.join(model_dir, "text_encoder", "config.json")) as f:
+        geo = models.clip_geometry_from_config(json.load(f))
+    csd = load_file(wpath)
+    # the null embedding exactly as the trainer makes it: the base encoder's output for the empty prompt, or the shipped SD2.1-base tensor when it fits
+    frozen = HipTextEncoder(geo, csd, 1, mode="autocast", device=device)
+    null_ids = torch.full((1, geo.max_pos), EOS, dtype=torch.int64, device=device)
+    null_ids[0, 0] = BOS
+    null = frozen.forward(null_ids, pins=False).clone()
+    del frozen
+    shipped = os.path.join("assets", "null_emb_sd21base.pt")
+    if os.path.exists(shipped):
+        t = torch.load(shipped, map_location="cpu")
+        t = t[0] if t.dim() == 3 else t
+        if tuple(t.shape) == tuple(null.shape[-2:]):
+            null = t.to(device, null.dtype).reshape(null.shape)
+    return BaseText(model_dir=model_dir, geo=geo, state_dict=csd, null=null)
+
+
+def load_text_encoder(model_dir: str, run: TrainedRun, batch: int, device="cuda", base: Optional[BaseText] = None):
+    """-> (HipTextEncoder, tokenizer): the base encoder in the trainer's autocast mode with the run's adapter, its tokens registered in the tokenizer
+    and written into the token table, and the null-embedding pins set (the reference's eval pipeline is a TextBoostModel, :176-182)."""
+    from . import checkpoint as ckpt
+    from .text_encoder import HipTextEncoder
+    base = base or load_base_text(model_dir, device)
+    geo = base.geo
+    tdir = os.path.join(model_dir, "tokenizer")
+    if not os.path.exists(os.path.join(tdir, "vocab.json")):
+        raise FileNotFoundError(f"{tdir}: no vocab.json (only local tokenizer files can be loaded)")
+    from transformers import CLIPTokenizer
+    tokenizer = CLIPTokenizer.from_pretrained(tdir, local_files_only=True)     # (train_textboost.load_tokenizer)
+    te = HipTextEncoder(geo, base.state_dict, batch, mode="autocast", lora_rank=run.rank, device=device)
+    if run.rank:
+        ckpt.load_lora_state_dict(te, run.lora)
+        te.pack_lora()
+    if run.tokens:
+        names = [n for n, _ in run.tokens]
+        for n, v in run.tokens:
+            if v.shape[0] != geo.hidden_size:
+                raise ValueError(f"{run.path}: token {n!r} has width {v.shape[0]}, the text encoder's hidden_size is {geo.hidden_size}")
+        if tokenizer.add_tokens(names) != len(names):
+            raise ValueError(f"{run.path}: the tokenizer already contains one of {names}")
+        ids = tokenizer.convert_tokens_to_ids(names)
+        rows = te.add_tokens([0] * len(names))
+        if list(rows) != list(ids):
+            raise ValueError(f"tokenizer ids {ids} and embedding rows {rows} disagree (tokenizer vocabulary != embedding table size)")
+        te.token_table[rows[0]:rows[0] + len(rows)].copy_(torch.stack([v for _, v in run.tokens]))
+    te.set_null_embedding(base.null)
+    return te, tokenizer
+
+
+def tokenize(tokenizer, prompts: Sequence[str], max_length: int) -> torch.Tensor:
+    return tokenizer(list(prompts), truncation=True, padding="max_length", max_length=max_length, return_tensors="pt").input_ids
+
+
+# ------------------------------------------------------------------------------------------------ the executors of a run
+class Pipeline:
+    """UNet (batch 2B: guidance), VAE decoder and sampler for B images per launch, on the fp16 build of the kernel library."""
+
+    def __init__(self, unet_geo, unet_sd, vae_geo, vae_sd, scheduler_config: Optional[dict], size: int, batch: int, steps: int = 25,
+                 guidance: float = 7.5, text_len: int = 77, device="cuda"):
+        from . import _lib
+        from .sampler import HipSampler
+        from .unet import HipUNet
+        from .vae import HipVAEDecoder
+        _lib.set_half("fp16")      # the reference's pipelines are fp16 (:321, inference.py:47)
+        self.size, self.B, self.steps, self.guidance, self.dev = size, batch, steps, guidance, device
+        self.unet = HipUNet(unet_geo, unet_sd, 2 * batch, size, size, text_len=text_len, device=device)
+        self.vae = HipVAEDecoder(vae_geo, vae_sd, batch, size, size, device=device)
+        self.sampler = HipSampler(self.unet, self.vae, steps=steps, guidance=guidance, scheduler_config=scheduler_config)
+
+    @classmethod
+    def from_model_dir(cls, model_dir: str, batch: int, steps: int = 25, guidance: float = 7.5, device="cuda"):
+        from safetensors.torch import load_file
+        from . import models
+        from .vae import VAEGeometry
+        for sub in ("unet", "vae", "text_encoder", "tokenizer", "scheduler"):
+            if not os.path.isdir(os.path.join(model_dir, sub)):
+                raise FileNotFoundError(f"{model_dir}: no {sub}/ (--model must be a local diffusers model directory)")
+        with open(os.path.join(model_dir, "unet", "config.json")) as f:
+            ucfg = json.load(f)
+        with open(os.path.join(model_dir, "vae", "config.json")) as f:
+            vcfg = json.load(f)
+        with open(os.path.join(model_dir, "scheduler", "scheduler_config.json")) as f:
+            scfg = json.load(f)
+        with open(os.path.join(model_dir, "text_encoder", "config.json")) as f:
+            text_len = json.load(f).get("max_position_embeddings", 77)
+        d = VAEGeometry()
+        vgeo = VAEGeometry(in_channels=vcfg.get("in_channels", d.in_channels), latent_channels=vcfg.get("latent_channels", d.latent_channels),
+                           block_out_channels=tuple(vcfg.get("block_out_channels", d.block_out_channels)),
+                           layers_per_block=vcfg.get("layers_per_block", d.layers_per_block),
+                           norm_num_groups=vcfg.get("norm_num_groups", d.norm_num_groups), scaling_factor=vcfg.get("scaling_factor", d.scaling_factor))
+        usd = load_file(os.path.join(model_dir, "unet", "diffusion_pytorch_model.safetensors"))
+        vsd = load_file(os.path.join(model_dir, "vae", "diffusion_pytorch_model.safetensors"))
+        return cls(models.unet_geometry_from_config(ucfg), usd, vgeo, vsd, scfg, int(ucfg.get("sample_size", 64)), batch, steps, guidance,
+                   text_len=text_len, device=device)
+
+    def images(self, cond, uncond, latents, what: str = "") -> torch.Tensor:
+        """text states fp32 [B*T, D] twice, latents fp32 [B, 4, size, size] on the device -> int32 RGBX [B, 8 size, 8 size] (resident).
+        Non-finite final latents raise before anything is decoded."""
+        x = self.sampler.denoise(cond, uncond, latents=latents)
+        if not bool(torch.isfinite(x).all()):
+            raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
+        return self.vae.decode_rgbx(x)
+
+
+# ------------------------------------------------------------------------------------------------ the protocol
+def _save_png(rgbx_host, path: str):
+    """one image of the downloaded RGBX buffer (int32 [H, W], little endian: R, G, B, X bytes) -> PNG with Pillow's defaults (the reference's bare
+    `image.save`)"""
+    from PIL import Image
+    h, w = rgbx_host.shape
+    Image.fromarray(rgbx_host.view("uint8").reshape(h, w, 4)[:, :, :3]).save(path)
+
+
+def generate_instance(pipe: Pipeline, base: BaseText, run: TrainedRun, instance: str, seeds: Sequence[int], outdir: str,
+                      token_format: str = "<INSTANCE> SUBJECT", prompt_batch: int = 16, pool: Optional[ThreadPoolExecutor] = None,
+                      timings: Optional[dict] = None) -> List[str]:
+    """`generate_from_pipeline` for every seed -> the PNG paths written.  `outdir` is the run's image root (`<outdir>/<basename>[-N][_desc]`)."""
+    dev = pipe.dev
+    identifier = identifier_for(token_format, instance, run.files)
+    prompts = instance_prompts(instance, identifier)
+    batches = prompt_batches(prompts, prompt_batch)
+    if max(len(b) for b in batches) > pipe.B:
+        raise ValueError(f"the executors are built for {pipe.B} prompts per batch; {max(len(b) for b in batches)} needed")
+    te, tokenizer = load_text_encoder(base.model_dir, run, 2 * pipe.B, dev, base=base)
+    T = base.geo.max_pos
+    # text states once per subject (they do not depend on the seed): the empty negative prompt and the batch's prompts in one encoder call
+    states = []
+    for b in batches:
+        padded = b + [b[-1]] * (pipe.B - len(b))
+        ids = tokenize(tokenizer, [""] * pipe.B + padded, T).to(dev)
+        out = te.forward(ids).view(2, pipe.B * T, -1)
+        states.append((out[1].clone(), out[0].clone()))
+    own_pool = pool is None
+    pool = pool or ThreadPoolExecutor(max_workers=MAX_PNG_THREADS)
+    written: List[str] = []
+    try:
+        for seed in seeds:
+            dst = os.path.join(outdir, f"seed{seed}", instance)
+            os.makedirs(dst, exist_ok=True)
+            lat = seeded_latent(seed, pipe.size).to(dev).repeat(pipe.B, 1, 1, 1)     # one latent for all prompts (:240, :257)
+            jobs = []
+            for b, (cond, uncond) in zip(batches, states):
+                t0 = time.perf_counter()
+                img = pipe.images(cond, uncond, lat, what=f"subject {instance}, seed {seed}, prompts {b}")
+                host = img[:len(b)].cpu().numpy()          # one download per batch (synchronises)
+                t1 = time.perf_counter()
+                for k, p in enumerate(b):
+                    path = os.path.join(dst, image_filename(p, identifier, instance))
+                    jobs.append(pool.submit(_save_png, host[k], path))
+                    written.append(path)
+                if timings is not None:
+                    timings["device_s"] = timings.get("device_s", 0.0) + (t1 - t0)
+                    timings["images"] = timings.get("images", 0) + len(b)
+            t0 = time.perf_counter()
+            for j in jobs:      # the seed's directory is complete before it is reported
+                j.result()
+            if timings is not None:
+                timings["png_wait_s"] = timings.get("png_wait_s", 0.0) + (time.perf_counter() - t0)
+            print(f"[seed {seed}] {instance}: {len(prompts)} images -> {dst} (identifier {identifier!r})")
+    finally:
+        if own_pool:
+            pool.shutdown(wait=True)
+    return written
+
+
+def generate_run(path: str, model_dir: str, instances: Sequence[str], seeds: Sequence[int], image_root: str, checkpoint: Optional[int] = None,
+                 token_format: str = "<INSTANCE> SUBJECT", steps: int = 25, guidance: float = 7.5, prompt_batch: int = 16, device="cuda") -> dict:
+    """`generate` (:270-350) over the subjects: executors once, the text encoder per subject.  -> {"images", "seconds", ...}"""
+    if not torch.cuda.is_available():
+        raise SystemExit("image generation needs an MI355X: the product path has no CPU fallback")
+    from . import _lib
+    _lib.set_half("fp16")
+    _lib.lib()
+    n_batch = max(len(b) for b in prompt_batches(list(range(25)), prompt_batch))
+    runs = {i: read_run_dir(model_path_of(path, i, checkpoint)) for i in instances}     # every refusal before anything reaches the device
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        pipe = Pipeline.from_model_dir(model_dir, n_batch, steps=steps, guidance=guidance, device=device)
+        base = load_base_text(model_dir, device)
+        timings: dict = {}
+        with ThreadPoolExecutor(max_workers=MAX_PNG_THREADS) as pool:
+            for i in instances:
+                generate_instance(pipe, base, runs[i], i, seeds, image_root, token_format=token_format, prompt_batch=prompt_batch, pool=pool,
+                                  timings=timings)
+    timings["seconds"] = time.perf_counter() - t0
+    n = timings.get("images", 0)
+    print(f"generated {n} images in {timings['seconds']:.1f} s ({n / max(timings.get('device_s', 0.0) + timings.get('png_wait_s', 0.0), 1e-9):.1f} "
+          f"images/s after setup; prompt batch {n_batch}, {steps} steps)")
+    return timings
+
+
+def check_model_dir(model: Optional[str], prog: str):
+    """--model: a local diffusers model directory; the reference's aliases name hub repositories"""
+    if model in HUB_ALIASES:
+        raise SystemExit(f"{prog}: --model {model} is the reference's alias of a hub repository; nothing is downloaded here: pass --model DIR, a "
+                         "local diffusers model directory (unet/, vae/, text_encoder/, tokenizer/, scheduler/)")
+    if not os.path.isdir(model):
+        raise SystemExit(f"{prog}: --model {model} is not a directory: pass --model DIR, a local diffusers model directory (unet/, vae/, "
+                         "text_encoder/, tokenizer/, scheduler/)")

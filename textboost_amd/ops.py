@@ -526,6 +526,13 @@ def vae_image(decoded, image, B, HW, C):
     L.check(L.lib().tb_vae_image(L.ptr(decoded), decoded.stride(0), L.ptr(image), B, HW, C, L.stream()), "tb_vae_image")
 
 
+def vae_image_rgbx(decoded, image, B, HW):
+    """decoded: fp32 [B*HW, >= 3] decoder output (row stride >= 3) -> image: int32 RGBX [B*HW] (contiguous), the resident image format."""
+    assert decoded.dtype == torch.float32 and decoded.stride(1) == 1 and decoded.shape[0] >= B * HW
+    assert image.dtype == torch.int32 and image.is_contiguous() and image.numel() >= B * HW
+    L.check(L.lib().tb_vae_image_rgbx(L.ptr(decoded), decoded.stride(0), L.ptr(image), B, HW, L.stream()), "tb_vae_image_rgbx")
+
+
 def conv_to4(x, w_packed, bias, out, B, H, W, C):
     if x.dtype == torch.float32:
         assert out.dtype == torch.float32

@@ -321,6 +321,23 @@ class HipVAEDecoder(HipVAEEncoder):
         conv("decoder.conv_out")
 
     def decode(self, latents):
+        geo, B = self.geo, self.B
+        rgb, H, W = self._decode_rgb(latents)
+        img = self.buf("image", B * geo.in_channels, H * W, torch.float32)
+        ops.vae_image(rgb, img, B, H * W, geo.in_channels)
+        return img.view(B, geo.in_channels, H, W)
+
+    def decode_rgbx(self, latents):
+        """the same decoder, finished as bytes: int32 RGBX [B, 8h, 8w], the resident image format of augment.py (`augment.to_host_rgb` downloads one
+        image) -- per channel uint8(rint(clamp(x / 2 + 0.5, 0, 1) * 255)), what diffusers' `numpy_to_pil` makes of `decode`'s image."""
+        assert self.geo.in_channels == 3
+        rgb, H, W = self._decode_rgb(latents)
+        img = self.buf("image_rgbx", self.B, H * W, torch.int32)
+        ops.vae_image_rgbx(rgb, img, self.B, H * W)
+        return img.view(self.B, H, W)
+
+    def _decode_rgb(self, latents):
+        """-> (fp32 NHWC rows [B*H*W, 4] of `vae.decode(latents / scaling_factor).sample`, 3 columns used; H; W)"""
         geo, B, H, W = self.geo, self.B, self.h, self.w
         L4 = geo.latent_channels
         ch = list(reversed(geo.block_out_channels))
@@ -346,9 +363,7 @@ class HipVAEDecoder(HipVAEEncoder):
         self._gn(x, "decoder.conv_norm_out", a, H * W, True)
         rgb = self.buf("rgb", B * H * W, 4, torch.float32)
         self._conv(a, "decoder.conv_out", rgb[:, :geo.in_channels], H, W, H, W)
-        img = self.buf("image", B * geo.in_channels, H * W, torch.float32)
-        ops.vae_image(rgb, img, B, H * W, geo.in_channels)
-        return img.view(B, geo.in_channels, H, W)
+        return rgb, H, W
 
 
 def vae_decoder_shapes(geo: VAEGeometry) -> Dict[str, Tuple[int, ...]]:
