@@ -222,12 +222,7 @@ def evaluate(args, evaluator=None, dino_evaluator=None):
     real_emb = {}
     if seen is not None:   # every real image once per run (the reference encodes them again for every seed)
         for name, table in (("seen", seen), ("unseen", unseen)):
-            flat = [p for i in instances for p in table[i]]
-            emb = ev.encode_images(flat, clip_i=True)
-            off, real_emb[name] = 0, {}
-            for i in instances:
-                real_emb[name][i] = emb[off:off + len(table[i])]
-                off += len(table[i])
+            real_emb[name] = split_by_instance(ev.encode_images([p for i in instances for p in table[i]], clip_i=True), table, instances)
     dino_real = None
     if db is not None:   # every real image once per run (the reference encodes them again for every seed)
         dino_real = split_by_instance(dev.encode_images([p for i in instances for p in db[i]]), db, instances)
@@ -240,11 +235,7 @@ def evaluate(args, evaluator=None, dino_evaluator=None):
             scores["clip_score"] = clip_t_scores(ev.encode_images(paths, clip_i=False), ev.encode_texts([prompt_of(p) for p in paths]))
             print(f"[seed {s}] CLIP-T: {scores['clip_score'].mean():.3f} +/- {scores['clip_score'].std():.3f} ({len(paths)} images)")
         if "clip-i" in args.metric:
-            emb = ev.encode_images(paths, clip_i=True)
-            gen_emb, off = {}, 0
-            for i in sorted(gen):
-                gen_emb[i] = emb[off:off + len(gen[i])]
-                off += len(gen[i])
+            gen_emb = split_by_instance(ev.encode_images(paths, clip_i=True), gen, sorted(gen))
             scores["clip_i"] = clip_i_means(gen_emb, real_emb["seen"])
             scores["clip_i_unseen"] = clip_i_means(gen_emb, real_emb["unseen"])
             print(f"[seed {s}] CLIP-I (seen): {scores['clip_i'].mean():.3f}  CLIP-I (unseen): {scores['clip_i_unseen'].mean():.3f}")

@@ -143,6 +143,30 @@ def test_full_size_vit_l14_336():
     assert cos.min().item() >= 0.9999, cos
 
 
+# recorded from HipCLIPVision.encode at the commit before the two towers moved onto vit.HipViT (this geometry, B = 3; the same in fp16 and bf16)
+_G = "gemm_kernel<64, 64, 0, 64, 4>"
+_BLOCK = ["layernorm_fwd", _G, "attn_fwd_kernel", _G, "layernorm_fwd", _G, _G]   # LN1, qkv, attention, out-proj, LN2, fc1, fc2
+TINY_TOWER_LAUNCHES = ["clip_patch_embed_kernel", "layernorm_fwd"] + 2 * _BLOCK + ["layernorm_fwd", _G]
+
+
+def test_tiny_tower_launch_schedule():
+    """the tower's launches, in order, by kernel: patch embedding, pre-LayerNorm, per block LN / qkv / attention / out-proj / LN / fc1 / fc2,
+    the final LayerNorm on the CLS rows, the projection"""
+    from textboost_amd import models, ops
+    from textboost_amd.clip_score import CLIPVisionGeometry, HipCLIPVision
+    from textboost_amd.text_encoder import CLIPGeometry
+    vg = CLIPVisionGeometry(image_size=224, patch_size=14, hidden_size=128, intermediate_size=512, num_layers=2, num_heads=2, projection_dim=64)
+    tg = CLIPGeometry(vocab_size=64, hidden_size=32, intermediate_size=64, num_layers=1, num_heads=2, max_pos=8)
+    tower = HipCLIPVision(vg, models.random_state_dict(models.clip_model_shapes(vg, tg), 9))
+    g = torch.Generator().manual_seed(3)
+    x = _rgbx(torch.randint(0, 256, (3, 224, 224, 3), generator=g, dtype=torch.uint8))
+    tower.encode(x)
+    ops.start_recording()
+    tower.encode(x)
+    names = [r[0] for r in ops.stop_recording()]
+    assert names == TINY_TOWER_LAUNCHES, names
+
+
 # ------------------------------------------------------------------------------------------------------------------ CLI end to end
 def _bytes_to_unicode():
     bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("¡"), ord("¬") + 1)) + list(range(ord("®"), ord("ÿ") + 1))

@@ -216,6 +216,28 @@ def test_full_size_vit_l14():
     assert rel <= 2e-3 and dcos <= 1e-4, (rel, dcos)   # measured 1.64e-3 and 2.0e-5
 
 
+# recorded from HipDINOv2.encode at the commit before the two towers moved onto vit.HipViT (this geometry, B = 3; the same in fp16 and bf16)
+_G = "gemm_kernel<64, 64, 0, 64, 4>"
+_BLOCK = ["layernorm_fwd", _G, "attn_fwd_kernel", _G, "layernorm_fwd", _G, _G]   # LN1, qkv, attention, out-proj, LN2, fc1, fc2
+TINY_TOWER_LAUNCHES = ["clip_patch_embed_kernel"] + 2 * _BLOCK + ["layernorm_fwd"]
+
+
+def test_tiny_tower_launch_schedule():
+    """the tower's launches, in order, by kernel: patch embedding, per block LN / qkv / attention / proj / LN / fc1 / fc2, the final LayerNorm
+    on the CLS rows"""
+    from textboost_amd import ops
+    from textboost_amd.dino_score import DINOv2Geometry, HipDINOv2
+    geo = DINOv2Geometry(hidden_size=128, intermediate_size=512, num_layers=2, num_heads=2, pos_grid=16)
+    tower = HipDINOv2(geo, _random_hub_state(geo, 31))
+    g = torch.Generator().manual_seed(3)
+    x = _rgbx(torch.randint(0, 256, (3, 224, 224, 3), generator=g, dtype=torch.uint8))
+    tower.encode(x)
+    ops.start_recording()
+    tower.encode(x)
+    names = [r[0] for r in ops.stop_recording()]
+    assert names == TINY_TOWER_LAUNCHES, names
+
+
 # ------------------------------------------------------------------------------------------------------------------ CLI end to end
 def test_cli_end_to_end(tmp_path):
     from PIL import Image

@@ -13,24 +13,22 @@ on the host and becomes a resident RGBX image (augment.py); the resizes are the 
 strided view and the tower reads it through `tb_clip_patch_embed` (csrc/clip_vision.hip), which folds CLIP's Normalize into its weight.
 
 Arithmetic is the text encoder's "autocast" mode for both towers: fp32 residual stream and LayerNorm statistics, 16-bit GEMM and attention
-operands.  (The reference runs CLIP-I in clip.load's fp16 model and CLIP-T in fp32 open_clip: DESIGN.md states the deviation.)
+operands; the image tower's schedule is vit.HipViT.  (The reference runs CLIP-I in clip.load's fp16 model and CLIP-T in fp32 open_clip: DESIGN.md.)
 """
 from __future__ import annotations
 
 import json
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import torch
 
 from . import _lib as L
 from . import augment, ops
 from .text_encoder import HF_LAYER, CLIPGeometry, HipTextEncoder
+from .vit import CLIP_MEAN, CLIP_STD, HipViT, ImageEvaluator, load_rgb, pack_patch_weight  # noqa: F401  (load_rgb: imported from here too)
 
-# OpenAI CLIP's Normalize (clip/clip.py `_transform`, open_clip OPENAI_DATASET_MEAN / STD)
-CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
-CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 CLIP_I_PRE_SIZE = 512   # eval_dreambooth.py:381 `v2.Resize((512, 512))`
 
 
@@ -84,91 +82,26 @@ def load_clip_model(model_dir: str):
     return vg, tg, eos, sd
 
 
-def pack_patch_weight(w: torch.Tensor, mean=CLIP_MEAN, std=CLIP_STD, dtype=None):
-    """conv weight [D, 3, p, p] -> (W' half [D, Kp], bias fp32 [D]) for `tb_clip_patch_embed`: Normalize folded in, K in the pixel layout's order
-    (ky, kx, R G B X) with a zero X column, zero columns up to the MFMA step."""
-    D, C, p, _ = w.shape
-    assert C == 3
-    w64 = w.detach().double().cpu()
-    m = torch.tensor(mean, dtype=torch.float64)
-    s = torch.tensor(std, dtype=torch.float64)
-    wk = torch.zeros(D, p, p, 4, dtype=torch.float64)
-    wk[..., :3] = (w64 / (255.0 * s[None, :, None, None])).permute(0, 2, 3, 1)
-    K = 4 * p * p
-    Kp = (K + 31) // 32 * 32
-    packed = torch.zeros(D, Kp, dtype=torch.float64)
-    packed[:, :K] = wk.reshape(D, K)
-    bias = -(w64 * (m / s)[None, :, None, None]).sum(dim=(1, 2, 3))
-    return packed.to(dtype or L.half_dtype()), bias.float()
-
-
-class HipCLIPVision:
-    """CLIPVisionModelWithProjection's forward (image_embeds), forward only, on the HIP kernels."""
+class HipCLIPVision(HipViT):
+    """CLIPVisionModelWithProjection's forward (image_embeds): the `vision_model.*` parameters of a transformers `CLIPModel` state dict and
+    `visual_projection` on the shared tower (vit.HipViT)."""
 
     def __init__(self, geo: CLIPVisionGeometry, state_dict: Dict[str, torch.Tensor], device="cuda"):
-        self.geo, self.dev = geo, device
         sd, pre = state_dict, "vision_model."
-        hd = L.half_dtype()
-        f16 = lambda t: t.detach().to(hd).to(device).contiguous()
-        f32 = lambda t: t.detach().float().to(device).contiguous()
-        f32r = lambda t: t.detach().to(hd).float().to(device).contiguous()   # bias rounded like the GEMM operands (text_encoder.py)
-        w, b = pack_patch_weight(sd[pre + "embeddings.patch_embedding.weight"])
-        self.patch_w, self.patch_b = w.to(device), b.to(device)
-        self.cls = f32(sd[pre + "embeddings.class_embedding"])
-        self.pos = f32(sd[pre + "embeddings.position_embedding.weight"])
-        assert self.pos.shape == (1 + geo.num_patches, geo.hidden_size), self.pos.shape
-        self.pre_g, self.pre_b = f32(sd[pre + "pre_layrnorm.weight"]), f32(sd[pre + "pre_layrnorm.bias"])
-        self.post_g, self.post_b = f32(sd[pre + "post_layernorm.weight"]), f32(sd[pre + "post_layernorm.bias"])
-        self.proj = f16(sd["visual_projection.weight"])
-        self.Wl: List[Dict[str, torch.Tensor]] = []
+        patch_w, patch_b = pack_patch_weight(sd[pre + "embeddings.patch_embedding.weight"], CLIP_MEAN, CLIP_STD)
+        layers = []
         for i in range(geo.num_layers):
             lp = f"{pre}encoder.layers.{i}."
-            W = {"qkv.w": f16(torch.cat([sd[lp + HF_LAYER[x] + ".weight"] for x in "qkv"], dim=0)),
-                 "qkv.b": f32r(torch.cat([sd[lp + HF_LAYER[x] + ".bias"] for x in "qkv"], dim=0))}
-            for n in ("out", "fc1", "fc2"):
-                W[n + ".w"], W[n + ".b"] = f16(sd[lp + HF_LAYER[n] + ".weight"]), f32r(sd[lp + HF_LAYER[n] + ".bias"])
-            for n in ("ln1", "ln2"):
-                W[n + ".g"], W[n + ".b"] = f32(sd[lp + HF_LAYER[n] + ".weight"]), f32(sd[lp + HF_LAYER[n] + ".bias"])
-            self.Wl.append(W)
-        self._bufs: Dict[int, Dict[str, torch.Tensor]] = {}
-
-    def _buffers(self, B: int):
-        b = self._bufs.get(B)
-        if b is None:
-            g = self.geo
-            M, D, I = B * (1 + g.num_patches), g.hidden_size, g.intermediate_size
-            hd, f32 = L.half_dtype(), torch.float32
-            z = lambda r, c, dt: torch.empty(r, c, device=self.dev, dtype=dt)
-            b = {"e": z(M, D, f32), "h": z(M, D, f32), "h2": z(M, D, f32), "x": z(M, D, hd), "qkv": z(M, 3 * D, hd), "o": z(M, D, hd),
-                 "a": z(M, I, hd), "ls": z(M, 2, f32), "lse": z(B * g.num_heads, 1 + g.num_patches, f32), "cls": z(B, D, hd),
-                 "cls_s": z(B, 2, f32)}
-            self._bufs = {B: b}   # one batch size at a time: the evaluation encodes full batches and one ragged tail
-        return b
-
-    def encode(self, images: torch.Tensor) -> torch.Tensor:
-        """images: int32 RGBX [B, S, S] (S = image_size; rows and images may be strided) -> fp32 [B, projection_dim] (unnormalised image_embeds)."""
-        g = self.geo
-        B, S, S2 = images.shape
-        if S != g.image_size or S2 != g.image_size:
-            raise ValueError(f"images are {S}x{S2}, the tower takes {g.image_size}x{g.image_size}")
-        T, D, H = 1 + g.num_patches, g.hidden_size, g.num_heads
-        bf = self._buffers(B)
-        e, h, h2, x, qkv, o, a, ls, lse = (bf[k] for k in ("e", "h", "h2", "x", "qkv", "o", "a", "ls", "lse"))
-        ops.clip_patch_embed(images, g.patch_size, self.patch_w, self.patch_b, self.cls, self.pos, e)
-        ops.layernorm_fwd(e, h, self.pre_g, self.pre_b, ls, g.eps)                       # pre_layrnorm: its output is the residual stream
-        for W in self.Wl:
-            ops.layernorm_fwd(h, x, W["ln1.g"], W["ln1.b"], ls, g.eps)
-            ops.gemm(x, W["qkv.w"], qkv, bias=W["qkv.b"])
-            ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], o, lse, B, H, T, T, D // H, causal=False)
-            ops.gemm(o, W["out.w"], h2, bias=W["out.b"], R=h)
-            ops.layernorm_fwd(h2, x, W["ln2.g"], W["ln2.b"], ls, g.eps)
-            ops.gemm(x, W["fc1.w"], a, bias=W["fc1.b"], act=L.ACT_QUICK_GELU)
-            ops.gemm(a, W["fc2.w"], h, bias=W["fc2.b"], R=h2)
-        cls_rows = h.as_strided((B, D), (T * D, 1))                                     # the CLS row of every image
-        ops.layernorm_fwd(cls_rows, bf["cls"], self.post_g, self.post_b, bf["cls_s"], g.eps)
-        out = torch.empty(B, g.projection_dim, device=self.dev, dtype=torch.float32)
-        ops.gemm(bf["cls"], self.proj, out)
-        return out
+            W = {"qkv.w": torch.cat([sd[lp + HF_LAYER[x] + ".weight"] for x in "qkv"], dim=0),
+                 "qkv.b": torch.cat([sd[lp + HF_LAYER[x] + ".bias"] for x in "qkv"], dim=0)}
+            for n in ("out", "fc1", "fc2", "ln1", "ln2"):
+                W[n + ".w"], W[n + ".b"] = sd[lp + HF_LAYER[n] + ".weight"], sd[lp + HF_LAYER[n] + ".bias"]
+            layers.append(W)
+        super().__init__(geo, patch_w=patch_w, patch_b=patch_b, cls=sd[pre + "embeddings.class_embedding"],
+                         pos=sd[pre + "embeddings.position_embedding.weight"], layers=layers,
+                         norm=(sd[pre + "post_layernorm.weight"], sd[pre + "post_layernorm.bias"]), act=L.ACT_QUICK_GELU, round_bias=True,
+                         pre_ln=(sd[pre + "pre_layrnorm.weight"], sd[pre + "pre_layrnorm.bias"]), proj=sd["visual_projection.weight"],
+                         device=device)
 
 
 class HipCLIPText:
@@ -210,41 +143,18 @@ def preprocess(img: torch.Tensor, size: int, clip_i: bool) -> torch.Tensor:
     return img[oy:oy + size, ox:ox + size]
 
 
-def load_rgb(path: str):
-    import numpy as np
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert("RGB"))
-
-
-class CLIPEvaluator:
+class CLIPEvaluator(ImageEvaluator):
     """Both towers of one CLIPModel directory plus the image / text batching of the two metrics."""
 
     def __init__(self, model_dir: str, batch_size: int = 32, device="cuda", tokenizer=None):
         vg, tg, eos, sd = load_clip_model(model_dir)
-        self.geo, self.batch_size, self.dev = vg, batch_size, device
-        self.vision = HipCLIPVision(vg, sd, device=device)
+        super().__init__(HipCLIPVision(vg, sd, device=device), batch_size, device)
         self.text = HipCLIPText(tg, sd, eos, batch=batch_size, device=device)
         self.tokenizer = tokenizer if tokenizer is not None else load_tokenizer(model_dir)
-        self.tower_seconds, self.tower_images = 0.0, 0
 
     def encode_images(self, paths: Sequence[str], clip_i: bool) -> torch.Tensor:
         """-> fp32 [len(paths), projection_dim] image_embeds, in batches of `batch_size`."""
-        S = self.geo.image_size
-        out = torch.empty(len(paths), self.geo.projection_dim, device=self.dev)
-        for i in range(0, len(paths), self.batch_size):
-            chunk = paths[i:i + self.batch_size]
-            batch = torch.empty(len(chunk), S, S, dtype=torch.int32, device=self.dev)
-            for j, p in enumerate(chunk):
-                batch[j].copy_(preprocess(augment.to_device_image(load_rgb(p)), S, clip_i))
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            out[i:i + len(chunk)] = self.vision.encode(batch)
-            t1.record()
-            t1.synchronize()
-            self.tower_seconds += t0.elapsed_time(t1) / 1e3
-            self.tower_images += len(chunk)
-        return out
+        return self.encode_paths(paths, lambda img, size: preprocess(img, size, clip_i))
 
     def encode_texts(self, texts: Sequence[str]) -> torch.Tensor:
         out = torch.empty(len(texts), self.geo.projection_dim, device=self.dev)
@@ -254,10 +164,6 @@ class CLIPEvaluator:
             ids = self.tokenizer(chunk, truncation=True, padding="max_length", max_length=T, return_tensors="pt").input_ids
             out[i:i + len(chunk)] = self.text.encode(ids)
         return out
-
-    def images_per_second(self) -> float:
-        return self.tower_images / self.tower_seconds if self.tower_seconds > 0 else 0.0
-
 
 def load_tokenizer(model_dir: str):
     """CLIPTokenizer from the model directory's vocab.json / merges.txt (local files only)."""

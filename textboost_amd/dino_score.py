@@ -13,28 +13,28 @@ the weights come in (`interpolate_pos_embed`: on the host, once, in fp32).
 
 Preprocessing [3P restated: torchvision's v2 transforms on PIL images]: Resize((512, 512)) then Resize((224, 224)), both Pillow BILINEAR with
 uint8 rounding in between, ToTensor, ImageNet Normalize.  Here the two resizes are the Pillow-exact kernels of csrc/image.hip and Normalize is
-folded into the patch weight of `tb_clip_patch_embed` (clip_score.pack_patch_weight), the conv bias added to the fold's bias.
+folded into the patch weight of `tb_clip_patch_embed` (vit.pack_patch_weight), the conv bias added to the fold's bias.
 
 Weights: the hub's checkpoint file (`dinov2_vitl14_pretrain.pth`, ViT-L/14 only) or a local transformers `Dinov2Model` directory (config.json +
 model.safetensors).  Both map onto one internal layout, the hub's parameter names and shapes.
 
-Arithmetic is the CLIP tower's (clip_score.py): fp32 residual stream and LayerNorm statistics, 16-bit GEMM and attention operands.  LayerScale
-is applied in fp32 in the epilogue of the GEMM that writes the residual stream (`tb_gemm_desc.col_scale`), never folded into the 16-bit weight:
-DINOv2 trains gamma from 1e-5, and gamma * W of that size would fall into fp16's subnormal range.
+The tower is vit.HipViT, the schedule the CLIP metrics run too: fp32 residual stream and LayerNorm statistics, 16-bit GEMM and attention operands.
+LayerScale is applied in fp32 in the epilogue of the GEMM that writes the residual stream (`tb_gemm_desc.col_scale`), never folded into the 16-bit
+weight: DINOv2 trains gamma from 1e-5, and gamma * W of that size would fall into fp16's subnormal range.  Linear biases stay fp32.
 """
 from __future__ import annotations
 
 import json
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from . import augment, ops
-from .clip_score import load_rgb, pack_patch_weight
+from . import augment
+from .vit import HipViT, ImageEvaluator, pack_patch_weight
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)   # eval_dreambooth.py:462 `v2.Normalize`
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -188,71 +188,23 @@ def interpolate_pos_embed(pos_embed: torch.Tensor, grid: int, offset: float = 0.
 
 
 # ------------------------------------------------------------------------------------------------------------------ the tower
-class HipDINOv2:
-    """DinoVisionTransformer's forward (the CLS row after the final LayerNorm), forward only, on the HIP kernels."""
+class HipDINOv2(HipViT):
+    """DinoVisionTransformer's forward (the CLS row after the final LayerNorm): a state dict in the hub's layout on the shared tower
+    (vit.HipViT)."""
 
     def __init__(self, geo: DINOv2Geometry, state: Dict[str, torch.Tensor], device="cuda"):
         check_hub_state(state, geo)
-        self.geo, self.dev = geo, device
-        hd = L.half_dtype()
-        f16 = lambda t: t.detach().to(hd).to(device).contiguous()
-        f32 = lambda t: t.detach().float().reshape(-1).to(device).contiguous()
-        w, b = pack_patch_weight(state["patch_embed.proj.weight"], IMAGENET_MEAN, IMAGENET_STD)
-        self.patch_w = w.to(device)
-        self.patch_b = (b.double() + state["patch_embed.proj.bias"].double()).float().to(device)
-        self.cls = f32(state["cls_token"])
-        self.pos = interpolate_pos_embed(state["pos_embed"], geo.grid, geo.interpolate_offset).to(device).contiguous()
-        self.norm_g, self.norm_b = f32(state["norm.weight"]), f32(state["norm.bias"])
-        self.Wl: List[Dict[str, torch.Tensor]] = []
+        patch_w, fold_b = pack_patch_weight(state["patch_embed.proj.weight"], IMAGENET_MEAN, IMAGENET_STD)
+        layers = []
         for i in range(geo.num_layers):
             b = f"blocks.{i}."
-            W = {}
-            for n, k in (("qkv", "attn.qkv"), ("proj", "attn.proj"), ("fc1", "mlp.fc1"), ("fc2", "mlp.fc2")):
-                W[n + ".w"], W[n + ".b"] = f16(state[b + k + ".weight"]), f32(state[b + k + ".bias"])
-            for n in ("norm1", "norm2"):
-                W[n + ".g"], W[n + ".b"] = f32(state[b + n + ".weight"]), f32(state[b + n + ".bias"])
-            W["ls1"], W["ls2"] = f32(state[b + "ls1.gamma"]), f32(state[b + "ls2.gamma"])
-            self.Wl.append(W)
-        self._bufs: Dict[int, Dict[str, torch.Tensor]] = {}
-
-    def _buffers(self, B: int):
-        b = self._bufs.get(B)
-        if b is None:
-            g = self.geo
-            T, D, I = g.num_tokens, g.hidden_size, g.intermediate_size
-            M = B * T
-            hd, f32 = L.half_dtype(), torch.float32
-            z = lambda r, c, dt: torch.empty(r, c, device=self.dev, dtype=dt)
-            b = {"h": z(M, D, f32), "h2": z(M, D, f32), "x": z(M, D, hd), "qkv": z(M, 3 * D, hd), "o": z(M, D, hd), "a": z(M, I, hd),
-                 "ls": z(M, 2, f32), "lse": z(B * g.num_heads, T, f32), "cls_s": z(B, 2, f32)}
-            self._bufs = {B: b}   # one batch size at a time: the evaluation encodes full batches and one ragged tail
-        return b
-
-    def encode(self, images: torch.Tensor) -> torch.Tensor:
-        """images: int32 RGBX [B, S, S] (S = image_size; rows and images may be strided) -> fp32 [B, D], the CLS rows after the final LayerNorm"""
-        g = self.geo
-        B, S, S2 = images.shape
-        if S != g.image_size or S2 != g.image_size:
-            raise ValueError(f"images are {S}x{S2}, the tower takes {g.image_size}x{g.image_size}")
-        T, D, H = g.num_tokens, g.hidden_size, g.num_heads
-        bf = self._buffers(B)
-        h, h2, x, qkv, o, a, ls, lse = (bf[k] for k in ("h", "h2", "x", "qkv", "o", "a", "ls", "lse"))
-        ops.clip_patch_embed(images, g.patch_size, self.patch_w, self.patch_b, self.cls, self.pos, h)
-        for W in self.Wl:
-            ops.layernorm_fwd(h, x, W["norm1.g"], W["norm1.b"], ls, g.eps)
-            ops.gemm(x, W["qkv.w"], qkv, bias=W["qkv.b"])
-            ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], o, lse, B, H, T, T, D // H, causal=False)
-            ops.gemm(o, W["proj.w"], h2, bias=W["proj.b"], R=h, col_scale=W["ls1"])      # x + ls1 * attn
-            ops.layernorm_fwd(h2, x, W["norm2.g"], W["norm2.b"], ls, g.eps)
-            ops.gemm(x, W["fc1.w"], a, bias=W["fc1.b"], act=L.ACT_GELU)
-            ops.gemm(a, W["fc2.w"], h, bias=W["fc2.b"], R=h2, col_scale=W["ls2"])        # x + ls2 * mlp
-        cls_rows = h.as_strided((B, D), (T * D, 1))                                       # the CLS row of every image
-        out = torch.empty(B, D, device=self.dev, dtype=torch.float32)
-        ops.layernorm_fwd(cls_rows, out, self.norm_g, self.norm_b, bf["cls_s"], g.eps)
-        if not bool(torch.isfinite(out).all()):
-            # 16-bit operands: the headroom of real DINOv2-L activations is not measured; a non-finite feature must not become a score
-            raise FloatingPointError("DINOv2 tower: non-finite CLS feature (a 16-bit GEMM / attention operand overflowed)")
-        return out
+            W = {"ls1": state[b + "ls1.gamma"], "ls2": state[b + "ls2.gamma"]}
+            for n, k in (("ln1", "norm1"), ("qkv", "attn.qkv"), ("out", "attn.proj"), ("ln2", "norm2"), ("fc1", "mlp.fc1"), ("fc2", "mlp.fc2")):
+                W[n + ".w"], W[n + ".b"] = state[b + k + ".weight"], state[b + k + ".bias"]
+            layers.append(W)
+        super().__init__(geo, patch_w=patch_w, patch_b=(fold_b.double() + state["patch_embed.proj.bias"].double()).float(),
+                         cls=state["cls_token"], pos=interpolate_pos_embed(state["pos_embed"], geo.grid, geo.interpolate_offset),
+                         layers=layers, norm=(state["norm.weight"], state["norm.bias"]), act=L.ACT_GELU, round_bias=False, device=device)
 
 
 # ------------------------------------------------------------------------------------------------------------------ evaluation
@@ -262,35 +214,16 @@ def preprocess(img: torch.Tensor, size: int = 224) -> torch.Tensor:
     return augment.resize(img, (size, size), augment.BILINEAR)
 
 
-class DINOEvaluator:
+class DINOEvaluator(ImageEvaluator):
     """the tower of one DINOv2 checkpoint plus the image batching of the metric"""
 
     def __init__(self, model_path: str, batch_size: int = 32, device="cuda"):
         geo, state = load_dino_model(model_path)
-        self.geo, self.batch_size, self.dev = geo, batch_size, device
-        self.tower = HipDINOv2(geo, state, device=device)
-        self.tower_seconds, self.tower_images = 0.0, 0
+        super().__init__(HipDINOv2(geo, state, device=device), batch_size, device)
 
     def encode_images(self, paths: Sequence[str]) -> torch.Tensor:
         """-> fp32 [len(paths), D] features, in batches of `batch_size`"""
-        S = self.geo.image_size
-        out = torch.empty(len(paths), self.geo.hidden_size, device=self.dev)
-        for i in range(0, len(paths), self.batch_size):
-            chunk = paths[i:i + self.batch_size]
-            batch = torch.empty(len(chunk), S, S, dtype=torch.int32, device=self.dev)
-            for j, p in enumerate(chunk):
-                batch[j].copy_(preprocess(augment.to_device_image(load_rgb(p)), S))
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            out[i:i + len(chunk)] = self.tower.encode(batch)
-            t1.record()
-            t1.synchronize()
-            self.tower_seconds += t0.elapsed_time(t1) / 1e3
-            self.tower_images += len(chunk)
-        return out
-
-    def images_per_second(self) -> float:
-        return self.tower_images / self.tower_seconds if self.tower_seconds > 0 else 0.0
+        return self.encode_paths(paths, preprocess)
 
 
 def dino_scores(generated: torch.Tensor, real: torch.Tensor, n_seen: int) -> Tuple[torch.Tensor, torch.Tensor]:
