@@ -34,6 +34,11 @@ _coeff_cache: "collections.OrderedDict[tuple, tuple]" = collections.OrderedDict(
 _COEFF_CACHE_MAX = 1024
 
 
+def clear_caches():
+    """drop the resident resample tables (they are rebuilt, with the same values, when a size comes up again)"""
+    _coeff_cache.clear()
+
+
 def _dev_table(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
 

@@ -267,7 +267,7 @@ class Pipeline:
     def from_model_dir(cls, model_dir: str, batch: int, steps: int = 25, guidance: float = 7.5, device="cuda"):
         from safetensors.torch import load_file
         from . import models
-        from .vae import VAEGeometry
+        from .vae import vae_geometry_from_config
         for sub in ("unet", "vae", "text_encoder", "tokenizer", "scheduler"):
             if not os.path.isdir(os.path.join(model_dir, sub)):
                 raise FileNotFoundError(f"{model_dir}: no {sub}/ (--model must be a local diffusers model directory)")
@@ -279,11 +279,7 @@ class Pipeline:
             scfg = json.load(f)
         with open(os.path.join(model_dir, "text_encoder", "config.json")) as f:
             text_len = json.load(f).get("max_position_embeddings", 77)
-        d = VAEGeometry()
-        vgeo = VAEGeometry(in_channels=vcfg.get("in_channels", d.in_channels), latent_channels=vcfg.get("latent_channels", d.latent_channels),
-                           block_out_channels=tuple(vcfg.get("block_out_channels", d.block_out_channels)),
-                           layers_per_block=vcfg.get("layers_per_block", d.layers_per_block),
-                           norm_num_groups=vcfg.get("norm_num_groups", d.norm_num_groups), scaling_factor=vcfg.get("scaling_factor", d.scaling_factor))
+        vgeo = vae_geometry_from_config(vcfg)
         usd = load_file(os.path.join(model_dir, "unet", "diffusion_pytorch_model.safetensors"))
         vsd = load_file(os.path.join(model_dir, "vae", "diffusion_pytorch_model.safetensors"))
         return cls(models.unet_geometry_from_config(ucfg), usd, vgeo, vsd, scfg, int(ucfg.get("sample_size", 64)), batch, steps, guidance,
@@ -385,11 +381,11 @@ def generate_run(path: str, model_dir: str, instances: Sequence[str], seeds: Seq
     return timings
 
 
-def check_model_dir(model: Optional[str], prog: str):
+def check_model_dir(model: Optional[str], prog: str, flag: str = "--model"):
     """--model: a local diffusers model directory; the reference's aliases name hub repositories"""
     if model in HUB_ALIASES:
-        raise SystemExit(f"{prog}: --model {model} is the reference's alias of a hub repository; nothing is downloaded here: pass --model DIR, a "
+        raise SystemExit(f"{prog}: {flag} {model} is the reference's alias of a hub repository; nothing is downloaded here: pass {flag} DIR, a "
                          "local diffusers model directory (unet/, vae/, text_encoder/, tokenizer/, scheduler/)")
     if not os.path.isdir(model):
-        raise SystemExit(f"{prog}: --model {model} is not a directory: pass --model DIR, a local diffusers model directory (unet/, vae/, "
+        raise SystemExit(f"{prog}: {flag} {model} is not a directory: pass {flag} DIR, a local diffusers model directory (unet/, vae/, "
                          "text_encoder/, tokenizer/, scheduler/)")

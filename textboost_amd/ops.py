@@ -788,6 +788,13 @@ def lora_bwd(dY, x, t, Bcat, dt, dA, dB, D, K, r, P, scaling=1.0, ws=None, w2_fw
 _sumsq_ws = {}
 
 
+def clear_step_workspaces():
+    """drop the scratch buffers that are keyed by a training step's shapes or addresses (`_lora_ws`, `_sumsq_ws`).  Only once no executor or
+    captured graph that was handed one of them will run again: they are allocated anew on the next use."""
+    _lora_ws.clear()
+    _sumsq_ws.clear()
+
+
 def sumsq(x, out):
     ws = _sumsq_ws.get((x.device, out.data_ptr()))
     if ws is None:

@@ -38,6 +38,15 @@ class VAEGeometry:
     scaling_factor: float = 0.18215
 
 
+def vae_geometry_from_config(cfg: dict) -> VAEGeometry:
+    """<model>/vae/config.json (diffusers AutoencoderKL) -> geometry; what the file leaves out is SD's"""
+    d = VAEGeometry()
+    return VAEGeometry(in_channels=cfg.get("in_channels", d.in_channels), latent_channels=cfg.get("latent_channels", d.latent_channels),
+                       block_out_channels=tuple(cfg.get("block_out_channels", d.block_out_channels)),
+                       layers_per_block=cfg.get("layers_per_block", d.layers_per_block),
+                       norm_num_groups=cfg.get("norm_num_groups", d.norm_num_groups), scaling_factor=cfg.get("scaling_factor", d.scaling_factor))
+
+
 def vae_encoder_shapes(geo: VAEGeometry) -> Dict[str, Tuple[int, ...]]:
     """diffusers AutoencoderKL state-dict keys of the encoder half (+ quant_conv) -> shapes."""
     S: Dict[str, Tuple[int, ...]] = {}

@@ -83,7 +83,73 @@ def check_resolution(resolution, unet_geo):
     check_latent_size(unet_geo, resolution // 8, resolution // 8)
 
 
-def main(args):
+class _Records(logging.Handler):
+    """keeps what is logged while models shared by several subjects are built, for every subject's own training.log"""
+
+    def __init__(self):
+        super().__init__()
+        self.records = []
+
+    def emit(self, record):
+        self.records.append(record)
+
+
+def _concepts(args):
+    """:602-615: one concept from the flags, or the --concepts_list JSON (a list of such dicts: multi-concept training)"""
+    if getattr(args, "concepts_list", None):
+        with open(args.concepts_list, "r") as f:
+            concepts = json.load(f)
+        for c in concepts:
+            c.setdefault("initializer_token", args.initializer_token)
+        return concepts
+    return [{"instance_data_dir": args.instance_data_dir, "placeholder_token": args.placeholder_token,
+             "initializer_token": args.initializer_token}]
+
+
+def _subject_inputs(args, have_tokenizer):
+    """What a subject trains from, and the latent side that follows from it -> (concepts, latents, pixels, use_images, latent)"""
+    from textboost_amd import data as tbdata
+    latent = args.resolution // 8
+    lat_path = os.path.join(args.instance_data_dir or "", "latents.pt")
+    latents = torch.load(lat_path) if args.instance_data_dir and os.path.exists(lat_path) else None
+    px_path = os.path.join(args.instance_data_dir or "", "pixel_values.pt")
+    pixels = torch.load(px_path) if args.instance_data_dir and os.path.exists(px_path) else None
+    concepts = _concepts(args)
+    use_images = have_tokenizer and all(tbdata.has_instance_images(c.get("instance_data_dir")) for c in concepts)
+    if use_images:
+        latents, pixels, latent = None, None, args.resolution // 8
+    if pixels is not None:
+        latents, latent = None, pixels.shape[-1] // 8
+    if latents is not None:
+        latent = latents.shape[-1]
+    return concepts, latents, pixels, use_images, latent
+
+
+def _validation_ids(args, clip_geo, have_tokenizer):
+    """log_validation's prompts (:453-531, :1212-1228) as token ids [P, T]: read tokenised when there is no tokenizer, else zeros that are filled
+    once the subject's tokens are registered; None when validation cannot run -> (ids, path looked at)"""
+    val_ids_path = os.path.join(args.instance_data_dir or "", "validation_input_ids.pt")
+    val_ids = torch.load(val_ids_path) if args.validation_prompts and os.path.exists(val_ids_path) else None
+    if args.validation_prompts and have_tokenizer:
+        val_ids = torch.zeros(len(args.validation_prompts), clip_geo.max_pos, dtype=torch.int64)  # filled once the tokens are registered
+    return val_ids, val_ids_path
+
+
+def _shared_key(args, n_val_images):
+    """the arguments the shared models are built from: subjects that agree in them can train on one context"""
+    return {"pretrained_model_name_or_path": args.pretrained_model_name_or_path, "tokenizer_name": getattr(args, "tokenizer_name", None),
+            "train_batch_size": args.train_batch_size, "resolution": args.resolution,
+            "mixed_precision": "no" if args.mixed_precision in (None, "no") else args.mixed_precision, "teacher": args.kpl_weight > 0,
+            "validation_images": n_val_images, "validation_scheduler": args.validation_scheduler}
+
+
+def setup_shared(args):
+    """Everything that depends only on the model directory, batch size, resolution and precision mode, and is frozen while a subject trains:
+    device / process group, the kernel library's 16-bit type, the training UNet, the validation sampler (its UNet and the VAE decoder), the VAE
+    encoder (built when the first subject that trains from pixels asks for it), the teacher text encoder, the null embedding, the CLIP state dict
+    students are built from, a pristine tokenizer and the edit prompts.  `train_subject(ctx, args)` trains one subject on it; a subject sweep
+    (textboost_amd/sweep.py) calls this once and that once per subject."""
+    import types
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -97,6 +163,9 @@ def main(args):
     if os.path.exists(ccfg):
         clip_geo = models.clip_geometry_from_config(json.load(open(ccfg)))
     check_resolution(args.resolution, unet_geo)
+    from textboost_amd.vae import VAEGeometry, vae_geometry_from_config
+    vcfg = os.path.join(mdir, "vae", "config.json")
+    vae_geo = vae_geometry_from_config(json.load(open(vcfg))) if os.path.exists(vcfg) else VAEGeometry()
     if not torch.cuda.is_available():
         raise SystemExit("train_textboost.py needs an MI355X: the product path has no CPU fallback")
     torch.cuda.set_device(local)
@@ -106,22 +175,31 @@ def main(args):
             raise ValueError("Gradient accumulation is not supported when training with multiple processes.")
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+        if not dist.is_initialized():   # (a sweep that builds a second context keeps its process group)
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     is_main = rank == 0
+    ctx = types.SimpleNamespace(world=world, rank=rank, local=local, dev=dev, is_main=is_main, unet_geo=unet_geo, clip_geo=clip_geo, vae_geo=vae_geo, trained=0,
+                                vae_encoder=None, vae_records=[], edit_prompts=None)
+    rec = _Records()   # what is logged here belongs into the training.log of every subject that trains on these models
     if is_main:
-        os.makedirs(args.output_dir, exist_ok=True)
-        fh = logging.FileHandler(os.path.join(args.output_dir, "training.log"))  # <output_dir>/training.log, :583-588
-        fh.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(name)s - %(message)s"))
-        logger.addHandler(fh)
+        logger.addHandler(rec)
         logger.setLevel(logging.INFO)
-    if args.seed is not None:
-        torch.manual_seed(args.seed)  # set_seed(args.seed): the same seed on every rank (:601)
+    try:
+        _build_shared(ctx, args)
+    finally:
+        logger.removeHandler(rec)
+    ctx.setup_records = rec.records
+    return ctx
+
+
+def _build_shared(ctx, args):
+    mdir = args.pretrained_model_name_or_path
+    dev, is_main, unet_geo, clip_geo = ctx.dev, ctx.is_main, ctx.unet_geo, ctx.clip_geo
     from textboost_amd import _lib
     _lib.lib()
     from textboost_amd.text_encoder import HipTextEncoder
-    from textboost_amd.trainer import StepHyper, TextBoostStep, shard_indices
     from textboost_amd.unet import HipUNet
-    from textboost_amd.workload import BOS, EOS, synthetic_ids
+    from textboost_amd.workload import BOS, EOS
 
     # ---- models (:629-656)
     usd = load_local_state_dict(os.path.join(mdir, "unet", "diffusion_pytorch_model.safetensors")) if os.path.isdir(mdir) else None
@@ -131,29 +209,11 @@ def main(args):
         usd = models.random_state_dict(models.unet_shapes(unet_geo), 1234, device=dev)
         csd = models.random_state_dict(models.clip_shapes(clip_geo), 1235, device=dev)
     B = args.train_batch_size
-    latent = args.resolution // 8
-    lat_path = os.path.join(args.instance_data_dir or "", "latents.pt")
-    latents = torch.load(lat_path) if args.instance_data_dir and os.path.exists(lat_path) else None
-    px_path = os.path.join(args.instance_data_dir or "", "pixel_values.pt")
-    pixels = torch.load(px_path) if args.instance_data_dir and os.path.exists(px_path) else None
-    tokenizer = load_tokenizer(mdir, getattr(args, "tokenizer_name", None))
-    from textboost_amd import data as tbdata
-    # :602-615: one concept from the flags, or the --concepts_list JSON (a list of such dicts: multi-concept training)
-    if getattr(args, "concepts_list", None):
-        with open(args.concepts_list, "r") as f:
-            concepts = json.load(f)
-        for c in concepts:
-            c.setdefault("initializer_token", args.initializer_token)
-    else:
-        concepts = [{"instance_data_dir": args.instance_data_dir, "placeholder_token": args.placeholder_token,
-                     "initializer_token": args.initializer_token}]
-    use_images = tokenizer is not None and all(tbdata.has_instance_images(c.get("instance_data_dir")) for c in concepts)
-    if use_images:
-        latents, pixels, latent = None, None, args.resolution // 8
-    if pixels is not None:
-        latents, latent = None, pixels.shape[-1] // 8
-    if latents is not None:
-        latent = latents.shape[-1]
+    # a tokenizer grows by a subject's tokens: the instance loaded here serves the first subject, every later one loads its own
+    ctx.tokenizer = load_tokenizer(mdir, getattr(args, "tokenizer_name", None))
+    ctx.have_tokenizer = ctx.tokenizer is not None
+    ctx.first_inputs = (args, _subject_inputs(args, ctx.have_tokenizer))   # read once: the first subject trains from these
+    latent = ctx.first_inputs[1][4]
     # --mixed_precision (:298-308): "fp16" = fp16 UNet / teacher, autocast text encoder with fp32 masters, dynamic loss scaling (:930-939);
     # unset / "no" = the default: weight_dtype float32, everything in fp32, no GradScaler (accelerate launch would otherwise take the mode from its
     # own config file; there is none here, so the flag alone decides)
@@ -164,27 +224,24 @@ def main(args):
     adt = torch.float32 if fp32_mode else _L.half_dtype()
     unet = HipUNet(unet_geo, usd, B, latent, latent, text_len=clip_geo.max_pos, device=dev, dtype=adt)
     # ---- validation sampling (:453-531, :1212-1228): prompts must arrive tokenised (no tokenizer offline)
-    val_ids_path = os.path.join(args.instance_data_dir or "", "validation_input_ids.pt")
-    val_ids = torch.load(val_ids_path) if args.validation_prompts and os.path.exists(val_ids_path) else None
-    if args.validation_prompts and tokenizer is not None:
-        val_ids = torch.zeros(len(args.validation_prompts), clip_geo.max_pos, dtype=torch.int64)  # filled once the tokens are registered
+    val_ids, val_ids_path = _validation_ids(args, clip_geo, ctx.have_tokenizer)
     sampler = None
     if args.validation_prompts and val_ids is None:
         logger.warning("--validation_prompts given but neither a tokenizer nor %s exists: validation is skipped", val_ids_path)
     if val_ids is not None and is_main:
         from textboost_amd.sampler import HipSampler
-        from textboost_amd.vae import HipVAEDecoder, VAEGeometry, vae_decoder_shapes
+        from textboost_amd.vae import HipVAEDecoder, vae_decoder_shapes
         nv = val_ids.shape[0] * args.num_validation_images
         dsd = load_local_state_dict(os.path.join(mdir, "vae", "diffusion_pytorch_model.safetensors")) if os.path.isdir(mdir) else None
         if dsd is None:
             logger.warning("no local VAE weights under %s: seeded random-init SD VAE decoder shapes are used for validation images", mdir)
-            dsd = models.random_state_dict(vae_decoder_shapes(VAEGeometry()), 1237, device=dev)
+            dsd = models.random_state_dict(vae_decoder_shapes(ctx.vae_geo), 1237, device=dev)
         # `scheduler_class.from_config(pipeline.scheduler.config)` (:493-495): betas, prediction_type, timestep_spacing ("leading": the PNDM /
         # DDIM instance's value) and steps_offset are inherited from the model's own scheduler
         scfg_path = os.path.join(mdir, "scheduler", "scheduler_config.json")
         scfg = json.load(open(scfg_path)) if os.path.exists(scfg_path) else None
         sampler = HipSampler(HipUNet(unet_geo, usd, 2 * nv, latent, latent, text_len=clip_geo.max_pos, device=dev),  # (validation images: fp16 pipeline in both modes)
-                             HipVAEDecoder(VAEGeometry(), dsd, nv, latent, latent, device=dev), steps=25, guidance=7.5,
+                             HipVAEDecoder(ctx.vae_geo, dsd, nv, latent, latent, device=dev), steps=25, guidance=7.5,
                              scheduler_config=scfg, scheduler=args.validation_scheduler)
         del dsd
     del usd
@@ -202,8 +259,83 @@ def main(args):
         if tuple(t.shape) == tuple(null.shape[-2:]):
             null = t.to(dev, null.dtype).reshape(null.shape)
             logger.info("null embedding loaded from %s", shipped)
-    te = HipTextEncoder(clip_geo, csd, B, mode=te_mode, lora_rank=args.lora_rank, n_slots=1, device=dev, seed=args.seed)
-    del csd
+    ctx.key = _shared_key(args, 0 if val_ids is None else val_ids.shape[0] * args.num_validation_images)
+    ctx.latent, ctx.unet, ctx.sampler, ctx.teacher, ctx.null, ctx.csd = latent, unet, sampler, teacher, null, csd
+
+
+def train_subject(ctx, args, final=True):
+    """One subject on the models of `setup_shared`: a fresh trainable text encoder, its tokens on a fresh tokenizer, the captured step, the loop,
+    checkpoints, validation images and the final save, logged to its own <output_dir>/training.log.  Nothing of it outlives the call: the next
+    subject starts from the state a process of its own would start from.  `final`: no subject follows (the process group is taken down and the
+    CLIP state dict released as soon as the student is built).  -> seconds spent in {capture, steps, validation, checkpoints, total}."""
+    val_ids = _validation_ids(args, ctx.clip_geo, ctx.have_tokenizer)[0]
+    key = _shared_key(args, 0 if val_ids is None else val_ids.shape[0] * args.num_validation_images)
+    if key != ctx.key:
+        diff = ", ".join(f"{k}: {ctx.key[k]!r} -> {v!r}" for k, v in key.items() if ctx.key[k] != v)
+        raise ValueError(f"this subject needs other shared models than the context holds ({diff})")
+    if args.unet_params_to_train == "crossattn_kv" and ctx.trained:
+        raise RuntimeError("--unet_params_to_train crossattn_kv writes adapters into the training UNet and the sampler's UNet: such a subject needs "
+                           "a context of its own (setup_shared per subject)")
+    fh = None
+    if ctx.is_main:
+        os.makedirs(args.output_dir, exist_ok=True)
+        fh = logging.FileHandler(os.path.join(args.output_dir, "training.log"))  # <output_dir>/training.log, :583-588
+        fh.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(name)s - %(message)s"))
+        logger.addHandler(fh)
+        logger.setLevel(logging.INFO)
+        for r in ctx.setup_records:
+            fh.handle(r)
+    try:
+        spent = _train_subject(ctx, args, final, fh, val_ids)
+    finally:
+        if fh is not None:
+            logger.removeHandler(fh)
+            fh.close()
+    release_subject_caches()
+    return spent
+
+
+def release_subject_caches():
+    """The process-wide device caches whose entries belong to one subject: the resample tables (keyed by the sizes its images and crops had) and
+    the sum-of-squares scratch (keyed by the address of its step's state).  Dropped once the subject's step is gone, so that a sweep's device
+    memory does not grow with the number of subjects; whatever is needed again is rebuilt with the same values."""
+    from textboost_amd import augment as tbaug
+    from textboost_amd import ops
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()   # the feeder's side stream may still read a table
+    tbaug.clear_caches()
+    ops.clear_step_workspaces()
+
+
+def _train_subject(ctx, args, final, fh, val_ids):
+    t_begin = time.perf_counter()
+    spent = {"capture": 0.0, "steps": 0.0, "validation": 0.0, "checkpoints": 0.0}
+    world, rank, dev, is_main, clip_geo = ctx.world, ctx.rank, ctx.dev, ctx.is_main, ctx.clip_geo
+    unet, sampler, teacher, null = ctx.unet, ctx.sampler, ctx.teacher, ctx.null
+    mdir = args.pretrained_model_name_or_path
+    if args.seed is not None:
+        torch.manual_seed(args.seed)  # set_seed(args.seed): the same seed on every rank (:601)
+    from textboost_amd import data as tbdata
+    from textboost_amd.text_encoder import HipTextEncoder
+    from textboost_amd.trainer import StepHyper, TextBoostStep, shard_indices
+    from textboost_amd.workload import BOS, EOS, synthetic_ids
+    B = args.train_batch_size
+    tokenizer, ctx.tokenizer = ctx.tokenizer, None
+    if tokenizer is None and ctx.have_tokenizer:
+        tokenizer = load_tokenizer(mdir, getattr(args, "tokenizer_name", None))
+    if ctx.first_inputs is not None and ctx.first_inputs[0] is args:
+        concepts, latents, pixels, use_images, latent = ctx.first_inputs[1]
+    else:
+        concepts, latents, pixels, use_images, latent = _subject_inputs(args, ctx.have_tokenizer)
+    ctx.first_inputs = None
+    if latent != ctx.latent:
+        raise ValueError(f"this subject's latents are {latent} x {latent}, the context's UNet was built for {ctx.latent} x {ctx.latent}")
+    fp32_mode = args.mixed_precision in (None, "no")
+    bf16_mode = args.mixed_precision == "bf16"
+    te_mode = "fp32" if fp32_mode else "autocast"
+    te = HipTextEncoder(clip_geo, ctx.csd, B, mode=te_mode, lora_rank=args.lora_rank, n_slots=1, device=dev, seed=args.seed)
+    if final:
+        ctx.csd = None
     te.set_null_embedding(null)
     if teacher is not None:
         teacher.set_null_embedding(null)
@@ -272,13 +404,24 @@ def main(args):
                                   "(textboost/utils.py:14-15) raises AttributeError in the reference itself")
     step = TextBoostStep(unet, te, teacher, hp, (B, 4, latent, latent), device=dev, world_size=world)
     if pixels is not None or use_images:  # :651-656, :938: the (frozen) VAE; the step then starts from pixel_values (:1027-1037)
-        from textboost_amd.vae import HipVAEEncoder, VAEGeometry, vae_encoder_shapes
-        vsd = load_local_state_dict(os.path.join(mdir, "vae", "diffusion_pytorch_model.safetensors")) if os.path.isdir(mdir) else None
-        if vsd is None:
-            logger.warning("no local VAE weights under %s: seeded random-init SD VAE encoder shapes are used", mdir)
-            vsd = models.random_state_dict(vae_encoder_shapes(VAEGeometry()), 1236, device=dev)
-        step.attach_vae(HipVAEEncoder(VAEGeometry(), vsd, B, 8 * latent, 8 * latent, device=dev))
-        del vsd
+        if ctx.vae_encoder is None:   # shared like the other frozen models; built here, where a single run has always built it
+            from textboost_amd.vae import HipVAEEncoder, vae_encoder_shapes
+            rec = _Records()
+            logger.addHandler(rec)
+            try:
+                vsd = load_local_state_dict(os.path.join(mdir, "vae", "diffusion_pytorch_model.safetensors")) if os.path.isdir(mdir) else None
+                if vsd is None:
+                    logger.warning("no local VAE weights under %s: seeded random-init SD VAE encoder shapes are used", mdir)
+                    vsd = models.random_state_dict(vae_encoder_shapes(ctx.vae_geo), 1236, device=dev)
+                ctx.vae_encoder = HipVAEEncoder(ctx.vae_geo, vsd, B, 8 * latent, 8 * latent, device=dev)
+                del vsd
+            finally:
+                logger.removeHandler(rec)
+            ctx.vae_records = rec.records
+        elif fh is not None:
+            for r in ctx.vae_records:
+                fh.handle(r)
+        step.attach_vae(ctx.vae_encoder)
 
     # ---- data: latents (+ ids) from disk, else synthetic; rank r takes samples r, r+W, ... (every shard non-empty: SURVEY 0.6)
     dg = torch.Generator().manual_seed(1000 + rank)
@@ -318,7 +461,9 @@ def main(args):
     edit_prompts = os.path.join("data", "human-written-prompts.jsonl")  # the reference's hard-coded relative path (:892)
     if tokenizer is not None and os.path.exists(edit_prompts):
         from textboost_amd.augment import PromptFeeder
-        prior_feeder = tbdata.PriorPromptFeeder(tbdata.read_edit_prompts(edit_prompts), feeder.tokenize if feeder is not None else
+        if ctx.edit_prompts is None:
+            ctx.edit_prompts = tbdata.read_edit_prompts(edit_prompts)
+        prior_feeder = tbdata.PriorPromptFeeder(ctx.edit_prompts, feeder.tokenize if feeder is not None else
                                                 PromptFeeder(tokenizer), additional_template=args.template,
                                                 additional_category=args.class_token, null_prob=args.null_prob, seed=args.seed or 0,
                                                 rank=rank, world=world)
@@ -414,7 +559,9 @@ def main(args):
         step.set_lr_table([lam(k) for k in range(args.max_train_steps + 1)])
     else:
         step.set_lr_multiplier(1.0)  # a resumed checkpoint's `state` may carry another schedule's multiplier: the lambdas are this run's (:911-916)
+    t_cap = time.perf_counter()
     step.capture(warmup=0)
+    spent["capture"] = time.perf_counter() - t_cap
     if feeder is not None:  # batch k+1 is produced on a side stream while step k runs (augment.PrefetchFeeder)
         from textboost_amd.augment import PrefetchFeeder
         prefetcher = PrefetchFeeder(feeder, B, step.pixel_values, step.input_ids)
@@ -436,18 +583,23 @@ def main(args):
                         sc["loss_kpl"], sc["loss_scale"], sc["grad_norm"])
             print(f"step {done}: loss {sc['loss']:.5f} lr {args.learning_rate}", flush=True)
         if sampler is not None and done % args.validation_steps == 0:  # :1212-1228
+            t_val = time.perf_counter()
             run_validation(done)
+            spent["validation"] += time.perf_counter() - t_val
         if is_main and done % args.checkpointing_steps == 0:  # :1157-1209
+            t_ck = time.perf_counter()
             ckpt.rotate_checkpoints(args.output_dir, args.checkpoints_total_limit)
             cdir = os.path.join(args.output_dir, f"checkpoint-{done}")
             ckpt.save_trainer_state(step, cdir)
             if args.lora_rank > 0:  # :1178-1182
                 ckpt.save_text_encoder_adapter(te, os.path.join(cdir, "text_encoder"), mdir)
             ckpt.save_token_embeddings(te, cdir, added_tokens, aug_token_dict if args.augment_inversion else None)
+            spent["checkpoints"] += time.perf_counter() - t_ck
         if prefetcher is not None and done < args.max_train_steps:
             # after the checkpoint, so that the generator states saved in it are those BEFORE the next batch's draws (resume replays them)
             prefetcher.prefetch(index_stream.take(B))
     torch.cuda.synchronize()
+    spent["steps"] = time.perf_counter() - t0 - spent["validation"] - spent["checkpoints"]
     if world > 1:
         import torch.distributed as dist
         dist.barrier()  # accelerator.wait_for_everyone() :1235
@@ -461,10 +613,26 @@ def main(args):
         logger.info("Training took %.2f seconds", dt)  # :1268-1269
         print(json.dumps({"steps": args.max_train_steps - first_step, "seconds": round(dt, 3),
                           "steps_per_s": round((args.max_train_steps - first_step) / max(dt, 1e-9), 3)}))
-    if world > 1:
+    if world > 1 and final:
         import torch.distributed as dist
         dist.destroy_process_group()
+    ctx.trained += 1
+    spent["total"] = time.perf_counter() - t_begin
+    return spent
 
+
+def main(args):
+    """One subject in a process of its own: the shared models, then the subject on them."""
+    ctx = setup_shared(args)
+    return train_subject(ctx, args)
+
+
+INPUT_ERROR_STATUS = 3   # the arguments or the data are wrong, the device is not: a sweep driver goes on to its next subject only after this one
 
 if __name__ == "__main__":
-    main(parse_args())
+    try:
+        main(parse_args())
+    except (FileNotFoundError, ValueError, NotImplementedError):
+        import traceback
+        traceback.print_exc()
+        sys.exit(INPUT_ERROR_STATUS)
