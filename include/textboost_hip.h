@@ -402,13 +402,14 @@ int tb_sumsq(const float* x, int64_t n, float* out, float* ws64 /* 64 floats scr
 /* GradScaler unscale/inf-check/update + clip_grad_norm_ coefficient + Adam bias corrections (:1108, :1128-1134).  grad_div >= 1 is the
  * data-parallel world size: the gradient buffers then hold the all-reduce SUM and DDP's division (:919-926) is folded into the unscale
  * coefficients state[TB_ST_COEF_*] and the reported norm -- no separate pass over the gradients */
-int tb_scaler_update(float* state, float max_norm, float beta1, float beta2, float growth_factor, float backoff_factor,
+int tb_scaler_update(float* state, float max_norm, double beta1, double beta2, float growth_factor, float backoff_factor,
                      float growth_interval, int use_scaler, float grad_div, tb_stream_t stream);
 /* lr_scheduler on the device: state[TB_ST_LR_MULT] = table[min(state[TB_ST_STEP], n - 1)] - 1 (table[k] = lambda(k) of diffusers
  * get_scheduler, :911-916); indexed by the number of optimizer steps that were not skipped, like accelerate's AcceleratedScheduler */
 int tb_lr_from_table(float* state, const float* table, int n, tb_stream_t stream);
-/* torch.optim.AdamW step on a flat fp32 buffer; g is multiplied by state[coef_slot]; skipped when state says inf */
-int tb_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
+/* torch.optim.AdamW step on a flat fp32 buffer; g is multiplied by state[coef_slot]; skipped when state says inf.  The betas are doubles, as
+ * torch holds them: 1 - beta is rounded to fp32 from the double difference and the bias corrections (tb_scaler_update) are formed in double */
+int tb_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, float wd,
              const float* state, int coef_slot, tb_stream_t stream);
 int tb_weight_decay(float* p, int64_t n, float factor, const float* state, tb_stream_t stream);
 /* added-row norm clamp (:1138-1149) and row norms for mean_norm (:1017) */
@@ -433,7 +434,8 @@ typedef struct {
   float decay_factor;                 /* 1 - emb_lr * wd at the base lr, as tb_weight_decay takes it */
   float* added_norms;                 /* [n_added] or NULL: row norms before the clamp */
   const float* lr_table; int32_t lr_table_n;
-  float lr, emb_lr, beta1, beta2, eps, wd, max_norm, mean_norm;
+  float lr, emb_lr, eps, wd, max_norm, mean_norm;
+  double beta1, beta2;                /* doubles, as torch holds them (see tb_adamw) */
   float growth_factor, backoff_factor, growth_interval; int32_t use_scaler; float grad_div;
   float* ws;
 } tb_opt_desc;

@@ -112,8 +112,8 @@ class OptDesc(C.Structure):
         ("p_decay", C.c_void_p), ("n_decay", C.c_int64), ("decay_factor", C.c_float),
         ("added_norms", C.c_void_p),
         ("lr_table", C.c_void_p), ("lr_table_n", C.c_int32),
-        ("lr", C.c_float), ("emb_lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("wd", C.c_float),
-        ("max_norm", C.c_float), ("mean_norm", C.c_float),
+        ("lr", C.c_float), ("emb_lr", C.c_float), ("eps", C.c_float), ("wd", C.c_float), ("max_norm", C.c_float), ("mean_norm", C.c_float),
+        ("beta1", C.c_double), ("beta2", C.c_double),
         ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_float), ("use_scaler", C.c_int32),
         ("grad_div", C.c_float),
         ("ws", C.c_void_p),
@@ -188,9 +188,9 @@ _SIGS = {
     "tb_boundary_conv_set_variant": ([_I], C.c_int),
     "tb_lora_bwd": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _I64, _I, _I, _I, _I, _F, _VP], C.c_int),
     "tb_sumsq": ([_VP, _I64, _VP, _VP, _VP], C.c_int),
-    "tb_scaler_update": ([_VP, _F, _F, _F, _F, _F, _F, _I, _F, _VP], C.c_int),
+    "tb_scaler_update": ([_VP, _F, C.c_double, C.c_double, _F, _F, _F, _I, _F, _VP], C.c_int),
     "tb_lr_from_table": ([_VP, _VP, _I, _VP], C.c_int),
-    "tb_adamw": ([_VP, _VP, _VP, _VP, _I64, _F, _F, _F, _F, _F, _VP, _I, _VP], C.c_int),
+    "tb_adamw": ([_VP, _VP, _VP, _VP, _I64, _F, C.c_double, C.c_double, _F, _F, _VP, _I, _VP], C.c_int),
     "tb_weight_decay": ([_VP, _I64, _F, _VP, _VP], C.c_int),
     "tb_renorm_rows": ([_VP, _I, _I, _F, _VP, _VP], C.c_int),
     "tb_row_norms": ([_VP, _I64, _I, _VP, _VP], C.c_int),

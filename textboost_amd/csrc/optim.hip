@@ -13,6 +13,26 @@
 
 namespace {
 
+// torch.optim.AdamW takes its betas as Python doubles: the bias corrections 1 - beta^step are formed in double from the step count, and 1 - beta
+// is rounded to fp32 ONCE from the double difference (`lerp_(grad, 1 - beta1)`, `addcmul_(grad, grad, value=1 - beta2)`).  Forming either from
+// the fp32-rounded beta instead is off by (beta - fl32(beta)) / (1 - beta): 1.3e-5 relative in every term of v at beta2 = 0.999 (found by
+// tests/test_gpu_optim.py).  Both forms of the tail below go through these two helpers.
+struct AdamBetas {
+  float b1, omb1, b2, omb2;   // fl32(beta), fl32(1 - beta)
+};
+__host__ __device__ __forceinline__ AdamBetas adam_betas(double beta1, double beta2) {
+  return AdamBetas{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2)};
+}
+// 1 - beta^step, step a non-negative integer held in a float (exact below 2^24): square-and-multiply in double, one rounding to fp32 at the end
+__device__ __forceinline__ float bias_correction(double beta, float step) {
+  double r = 1.0;
+  for (unsigned k = (unsigned)step; k; k >>= 1) {
+    if (k & 1) r *= beta;
+    beta *= beta;
+  }
+  return (float)(1.0 - r);
+}
+
 // deterministic sum of squares: 64 blocks write partials, the LAST-launched tiny kernel adds them in a fixed order
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
   __shared__ float red[4];
@@ -32,7 +52,7 @@ __global__ void sumsq_final_kernel(const float* __restrict__ part, int nb, float
 }
 
 // one thread: derive every per-step scalar from the two gradient sums of squares
-__global__ void scaler_update_kernel(float* __restrict__ st, float max_norm, float beta1, float beta2, float growth_factor,
+__global__ void scaler_update_kernel(float* __restrict__ st, float max_norm, double beta1, double beta2, float growth_factor,
                                      float backoff_factor, float growth_interval, int use_scaler, float grad_div) {
   const float scale = st[TB_ST_LOSS_SCALE];
   const float ss_lora = st[TB_ST_SUMSQ_LORA], ss_emb = st[TB_ST_SUMSQ_EMB];
@@ -42,7 +62,8 @@ __global__ void scaler_update_kernel(float* __restrict__ st, float max_norm, flo
   // grad_div = data-parallel world size: the gradient buffer holds the all-reduce SUM, DDP's mean is folded into the coefficients here
   const float inv = 1.f / (scale * grad_div);
   const float total = sqrtf(ss_lora) * inv;                      // norm of the unscaled LoRA grads
-  const float clip = fminf(max_norm / (total + 1e-6f), 1.f);    // torch clip_grad_norm_
+  const float cc = max_norm / (total + 1e-6f);                   // torch clip_grad_norm_: clamp(max_norm / (total + 1e-6), max=1), which keeps a
+  const float clip = cc > 1.f ? 1.f : cc;                        // NaN norm a NaN coefficient (fminf would turn it into 1)
   st[TB_ST_FOUND_INF] = found_inf ? 1.f : 0.f;
   st[TB_ST_GRAD_NORM] = total;
   st[TB_ST_COEF_LORA] = inv * clip;
@@ -50,8 +71,8 @@ __global__ void scaler_update_kernel(float* __restrict__ st, float max_norm, flo
   if (!found_inf) {
     const float step = st[TB_ST_STEP] + 1.f;
     st[TB_ST_STEP] = step;
-    st[TB_ST_BC1] = 1.f - powf(beta1, step);
-    st[TB_ST_BC2] = 1.f - powf(beta2, step);
+    st[TB_ST_BC1] = bias_correction(beta1, step);
+    st[TB_ST_BC2] = bias_correction(beta2, step);
   }
   if (use_scaler) {  // torch.cuda.amp.GradScaler.update()
     if (found_inf) {
@@ -79,7 +100,7 @@ __global__ void lr_from_table_kernel(float* __restrict__ st, const float* __rest
 
 // torch.optim.AdamW (decoupled decay first, then Adam update with bias corrections), grads pre-multiplied by coef
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                                    float* __restrict__ v, int64_t n, float lr, AdamBetas be, float eps,
                                                     float wd, const float* __restrict__ st, int coef_slot) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -88,8 +109,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   const float bc1 = st[TB_ST_BC1], bc2 = st[TB_ST_BC2];
   lr *= 1.f + st[TB_ST_LR_MULT];  // LambdaLR: every group's lr is its base lr times lambda(step) (slot holds lambda - 1)
   float pi = p[i] * (1.f - lr * wd);
-  const float mi = beta1 * m[i] + (1.f - beta1) * gi;
-  const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+  const float mi = be.b1 * m[i] + be.omb1 * gi;
+  const float vi = be.b2 * v[i] + be.omb2 * gi * gi;
   m[i] = mi;
   v[i] = vi;
   const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
@@ -108,6 +129,8 @@ __global__ __launch_bounds__(256) void decay_kernel(float* __restrict__ p, int64
 }
 
 // w[a] <- w[a] * min(mean_norm, |w[a]|) / |w[a]| ; norms[a] = |w[a]| before clamping  (:1143-1149)
+// An all-zero row gives min(mean_norm, 0) / 0 = NaN and becomes a NaN row.  So it does in the reference, which has no guard either: :1146-1149
+// compute (scale / v_norm) * added_embeddings with scale = v_norm = 0.  Kept as is (tests/test_gpu_optim.py pins it).
 __global__ __launch_bounds__(256) void renorm_rows_kernel(float* __restrict__ w, int D, float mean_norm, float* __restrict__ norms) {
   __shared__ float red[4];
   float* row = w + (int64_t)blockIdx.x * D;
@@ -185,7 +208,8 @@ __device__ __forceinline__ OptScalars opt_scalars(const tb_opt_desc& d) {
   const bool found_inf = d.use_scaler && !(isfinite(o.ss_lora) && isfinite(o.ss_emb));
   const float inv = 1.f / (o.scale * d.grad_div);
   o.total = sqrtf(o.ss_lora) * inv;
-  const float clip = fminf(d.max_norm / (o.total + 1e-6f), 1.f);
+  const float cc = d.max_norm / (o.total + 1e-6f);
+  const float clip = cc > 1.f ? 1.f : cc;                        // (= scaler_update_kernel: NaN stays NaN)
   o.found_inf = found_inf ? 1.f : 0.f;
   o.coef_lora = inv * clip;
   o.coef_emb = inv;
@@ -193,17 +217,20 @@ __device__ __forceinline__ OptScalars opt_scalars(const tb_opt_desc& d) {
   o.bc1 = o.bc2 = 1.f;
   return o;
 }
+// (every thread of an AdamW workgroup runs this double loop, ~11 rounds per beta, and adam_betas per element: block-uniform work kept per thread so
+//  that it is the one-thread arithmetic of scaler_update_kernel bit for bit; it does not show in the step time)
 __device__ __forceinline__ void opt_bias_corrections(OptScalars& o, const tb_opt_desc& d) {   // (the roles that run AdamW, and the publisher)
-  o.bc1 = 1.f - powf(d.beta1, o.step);
-  o.bc2 = 1.f - powf(d.beta2, o.step);
+  o.bc1 = bias_correction(d.beta1, o.step);
+  o.bc2 = bias_correction(d.beta2, o.step);
 }
 __device__ __forceinline__ void opt_adamw_elem(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                int64_t i, float lr, float coef, const OptScalars& o, const tb_opt_desc& d) {  // = adamw_kernel
+  const AdamBetas be = adam_betas(d.beta1, d.beta2);
   const float gi = g[i] * coef;
   lr *= 1.f + o.lr_mult;
   float pi = p[i] * (1.f - lr * d.wd);
-  const float mi = d.beta1 * m[i] + (1.f - d.beta1) * gi;
-  const float vi = d.beta2 * v[i] + (1.f - d.beta2) * gi * gi;
+  const float mi = be.b1 * m[i] + be.omb1 * gi;
+  const float vi = be.b2 * v[i] + be.omb2 * gi * gi;
   m[i] = mi;
   v[i] = vi;
   const float denom = sqrtf(vi) / sqrtf(o.bc2) + d.eps;
@@ -263,7 +290,7 @@ __global__ __launch_bounds__(256) void opt_apply_kernel(const tb_opt_desc d, int
     float a = 0.f;
     for (int c = t; c < d.D; c += 256) a += row[c] * row[c];   // (a thread re-reads exactly the elements it wrote)
     const float nrm = sqrtf(block_sum_256(a, red));
-    const float f = fminf(d.mean_norm, nrm) / nrm;
+    const float f = fminf(d.mean_norm, nrm) / nrm;   // (an all-zero row: 0 / 0 = NaN, as in renorm_rows_kernel and in the reference, :1146-1149)
     for (int c = t; c < d.D; c += 256) row[c] *= f;
     if (t == 0 && d.added_norms) d.added_norms[r] = nrm;
     return;
@@ -313,7 +340,7 @@ extern "C" int tb_sumsq(const float* x, int64_t n, float* out, float* ws64, tb_s
   return TB_OK;
 }
 
-extern "C" int tb_scaler_update(float* state, float max_norm, float beta1, float beta2, float growth_factor, float backoff_factor,
+extern "C" int tb_scaler_update(float* state, float max_norm, double beta1, double beta2, float growth_factor, float backoff_factor,
                                 float growth_interval, int use_scaler, float grad_div, tb_stream_t stream) {
   (void)hipGetLastError();  // drop any stale (non-sticky) error left by an earlier runtime call
   if (!state || !(grad_div >= 1.f)) return TB_EINVAL;
@@ -331,12 +358,12 @@ extern "C" int tb_lr_from_table(float* state, const float* table, int n, tb_stre
   return TB_OK;
 }
 
-extern "C" int tb_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
+extern "C" int tb_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps, float wd,
                         const float* state, int coef_slot, tb_stream_t stream) {
   (void)hipGetLastError();  // drop any stale (non-sticky) error left by an earlier runtime call
   if (!p || !g || !m || !v || !state || n <= 0) return TB_EINVAL;
   if (coef_slot != TB_ST_COEF_LORA && coef_slot != TB_ST_COEF_EMB) return TB_EINVAL;
-  hipLaunchKernelGGL(adamw_kernel, GRID1D(n), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, wd, state,
+  hipLaunchKernelGGL(adamw_kernel, GRID1D(n), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, adam_betas(beta1, beta2), eps, wd, state,
                      coef_slot);
   TB_CHECK_LAUNCH();
   return TB_OK;
