@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Image generation and CLIP-T / CLIP-I / DINO evaluation of a trained DreamBooth run: the reference's eval_dreambooth.py (`generate` :270-350,
-`clip_score` :353-374, `clip_i` :377-453, `dino_score` :456-543, the CSV of `main` :568-628) with the same flags, on the HIP executors of
-textboost_amd/generate.py (text encoder with the trained adapter and tokens, guided DPM-Solver++ sampling, VAE decoder), the HIP CLIP ViT-L/14
-of textboost_amd/clip_score.py and the HIP DINOv2 ViT-L/14 of textboost_amd/dino_score.py.
+"""Image generation and CLIP-T / CLIP-I / DINO / VQA evaluation of a trained DreamBooth run: the reference's eval_dreambooth.py (`generate`
+:270-350, `clip_score` :353-374, `clip_i` :377-453, `dino_score` :456-543, `vqa_score` :546-565, the CSV of `main` :568-628) with the same
+flags, on the HIP executors of textboost_amd/generate.py (text encoder with the trained adapter and tokens, guided DPM-Solver++ sampling, VAE
+decoder), the HIP CLIP ViT-L/14 of textboost_amd/clip_score.py, the HIP DINOv2 ViT-L/14 of textboost_amd/dino_score.py and the HIP
+CLIP-FlanT5 encoder-decoder of textboost_amd/vqa_score.py.
 
     python eval_dreambooth.py <path> --model <diffusers model dir> --metric clip-t clip-i dino --clip-model <CLIPModel dir> \
         --dino-model <DINOv2 weights> [--instances dog can ...] [--token-format "<INSTANCE> SUBJECT"] [--prompt-batch 16]
     python eval_dreambooth.py <path> --skip-gen --metric clip-t clip-i dino --clip-model <CLIPModel dir> --dino-model <DINOv2 weights> \
         [--outdir ./benchmarks] [--seeds 0 1 2 3] [--train-dir ...] [--val-dir ...] [--dreambooth-path ./data/dreambooth] [--checkpoint N]
         [--output-desc D]
+    python eval_dreambooth.py <path> --skip-gen --metric clip-t clip-i vqa --clip-model <CLIPModel dir> --vqa-model <clip-flant5 dir>
 
 Without --skip-gen the images are generated first: for every subject (`--instances`, else those of the 30 DreamBooth subjects that exist as
 sub-directories of `path`) the trained output directory `<path>/<instance>[/checkpoint-<N>]` is read back (text_encoder/ adapter, `<token>.bin`),
@@ -25,7 +27,11 @@ Images are read from `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/
 takes N, the number of seen ones, from `path` as the reference does (`<name>-<model>-n<N>`, e.g. `out/tb-sd15-n1`): an instance's first N real
 images are seen, the rest unseen.
 
-Not built here: the VQA score (FlanT5-XXL): asking for it is an error, so that a 0.000 placeholder in the CSV never reads as a score."""
+--vqa-model names a local clip-flant5 directory (config.json, safetensors or .bin shards with the T5 and `mm_projector` weights, the T5
+tokenizer files): it replaces the reference's download of t2v_metrics' `clip-flant5-xxl`; its vision tower is the one of --clip-model.  The
+score of an image is P("Yes") for the question 'Does this figure show "<file name>"? Please answer yes or no.', in bfloat16 arithmetic.
+
+Without --vqa-model the VQA score is not built: asking for it is an error, so that a 0.000 placeholder in the CSV never reads as a score."""
 from __future__ import annotations
 
 import argparse
@@ -62,6 +68,8 @@ def build_parser():
     p.add_argument("--clip-model", type=str, default=None, help="local transformers CLIPModel directory (ViT-L/14@336px) with its tokenizer files")
     p.add_argument("--dino-model", type=str, default=None,
                    help="DINOv2 ViT-L/14 weights: the hub's dinov2_vitl14_pretrain.pth or a local transformers Dinov2Model directory")
+    p.add_argument("--vqa-model", type=str, default=None,
+                   help="local clip-flant5 directory (config.json, T5 + mm_projector weights, tokenizer files); its vision tower is --clip-model's")
     p.add_argument("--batch-size", type=int, default=32, help="images per tower launch")
     return p
 
@@ -79,10 +87,14 @@ def check_args(args):
     unknown = [m for m in args.metric if m not in BUILT_METRICS + ("vqa",)]
     if unknown:
         raise SystemExit(f"eval_dreambooth.py: unknown --metric {unknown}")
-    missing = [m for m in args.metric if m not in BUILT_METRICS]
+    missing = [m for m in args.metric if m not in BUILT_METRICS and not (m == "vqa" and args.vqa_model)]
     if missing:
         raise SystemExit(f"eval_dreambooth.py: --metric {' '.join(missing)} is not built (only CLIP-T, CLIP-I and DINO are); "
-                         "pass --metric clip-t clip-i dino, or some of them")
+                         "pass --metric clip-t clip-i dino, or some of them.  The VQA score is built with --vqa-model DIR (a local "
+                         "clip-flant5 directory) and --clip-model DIR")
+    if "vqa" in args.metric and not args.clip_model:
+        raise SystemExit("eval_dreambooth.py: --metric vqa needs --clip-model DIR (a local CLIPModel directory): the VQA model's vision tower "
+                         "is CLIP ViT-L/14@336px")
     if "dino" in args.metric and not args.dino_model:
         raise SystemExit("eval_dreambooth.py: --metric dino needs --dino-model PATH (the hub's dinov2_vitl14_pretrain.pth or a local "
                          "Dinov2Model directory)")
@@ -200,7 +212,7 @@ def dino_means(gen_emb: Dict[str, "object"], real_emb: Dict[str, "object"], n_se
     return torch.cat([p[0] for p in pairs]), torch.cat([p[1] for p in pairs])
 
 
-def evaluate(args, evaluator=None, dino_evaluator=None):
+def evaluate(args, evaluator=None, dino_evaluator=None, vqa_evaluator=None):
     """-> {seed: {metric: per-sample scores}}; writes the CSV."""
     from textboost_amd.clip_score import CLIPEvaluator, clip_t_scores, prompt_of
     root = image_root(args)
@@ -219,6 +231,10 @@ def evaluate(args, evaluator=None, dino_evaluator=None):
     if db is not None:
         from textboost_amd.dino_score import DINOEvaluator
         dev = dino_evaluator or DINOEvaluator(args.dino_model, batch_size=args.batch_size)
+    vev = None
+    if "vqa" in args.metric:
+        from textboost_amd.vqa_score import VQAEvaluator
+        vev = vqa_evaluator or VQAEvaluator(args.vqa_model, args.clip_model, batch_size=args.batch_size)
     real_emb = {}
     if seen is not None:   # every real image once per run (the reference encodes them again for every seed)
         for name, table in (("seen", seen), ("unseen", unseen)):
@@ -234,6 +250,11 @@ def evaluate(args, evaluator=None, dino_evaluator=None):
         if "clip-t" in args.metric:
             scores["clip_score"] = clip_t_scores(ev.encode_images(paths, clip_i=False), ev.encode_texts([prompt_of(p) for p in paths]))
             print(f"[seed {s}] CLIP-T: {scores['clip_score'].mean():.3f} +/- {scores['clip_score'].std():.3f} ({len(paths)} images)")
+        if vev is not None:
+            scores["vqa_score"] = vev.score_paths(paths, [prompt_of(p) for p in paths])
+            print(f"[seed {s}] VQA score: {scores['vqa_score'].mean():.3f} +/- {scores['vqa_score'].std():.3f} ({len(paths)} images)")
+            if s == args.seeds[-1]:
+                vev.release()   # 22 GB of weights at full size: freed as soon as the last seed is scored
         if "clip-i" in args.metric:
             gen_emb = split_by_instance(ev.encode_images(paths, clip_i=True), gen, sorted(gen))
             scores["clip_i"] = clip_i_means(gen_emb, real_emb["seen"])
@@ -253,6 +274,8 @@ def evaluate(args, evaluator=None, dino_evaluator=None):
         print(f"image tower: {ev.tower_images} images, {ev.images_per_second():.1f} images/s ({ev.geo.image_size} px, batch {ev.batch_size})")
     if dev is not None:
         print(f"DINO tower: {dev.tower_images} images, {dev.images_per_second():.1f} images/s ({dev.geo.image_size} px, batch {dev.batch_size})")
+    if vev is not None:
+        print(f"VQA model: {vev.images} images, {vev.images_per_second():.1f} images/s (batch {vev.batch_size})")
     print(f"wrote {out}")
     return results
 

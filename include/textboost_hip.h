@@ -522,6 +522,24 @@ int tb_img_unpack_rgb(const uint32_t* src, int64_t sstride, int w, int h, uint8_
 int tb_clip_patch_embed(const uint32_t* img, int64_t img_stride, int64_t row_stride, int B, int S, int patch, const void* w, int64_t ldw,
                         int Kp, const float* bias, const float* cls, const float* pos, float* out, int64_t ldo, int D, tb_stream_t stream);
 
+/* ---- T5 operations (csrc/t5.hip; the CLIP-FlanT5 encoder-decoder of the VQA score, textboost_amd/vqa_score.py; reference
+ * eval_dreambooth.py:546-565, transformers T5LayerNorm / T5Attention / T5DenseGatedActDense) ------------------------------------------------
+ * tb_rmsnorm_fwd: y[m, c] = x[m, c] * rsqrt(mean_c(x[m]^2) + eps) * gamma[c] in fp32 -- no mean subtraction, no bias.  x fp32 [M, C] (row
+ * stride ldx: rows may be strided), y TB_F16 or TB_F32 (y_dtype), gamma fp32 [C]. */
+int tb_rmsnorm_fwd(const float* x, int64_t ldx, void* y, int64_t ldy, int y_dtype, const float* gamma, int64_t M, int C, float eps,
+                   tb_stream_t stream);
+/* tb_attention_rel_fwd: tb_attention_fwd's O = softmax(scale Q K^T + bias [+ causal]) V with T5's relative-position bias and a key-padding
+ * length.  Q / K / V / O, their leading dimensions, `scale`, `causal` and `LSE` (may be NULL) as in tb_attention_fwd (T5 passes scale = 1); the
+ * other fields of the descriptor are not read.
+ *   rel     NULL or fp32 [H, Sq + Skv - 1]: the bias of query i and key j is rel[h][j - i + Sq - 1], added in fp32 to scale * QK^T (T5's bias
+ *           depends on (h, j - i) only, so [H, Sq, Skv] is never materialised)
+ *   kv_len  NULL or int32 [B]: keys j >= kv_len[b] are masked and tiles wholly beyond it skipped; a batch of length 0 gets O = 0, LSE = -inf
+ * hd == 64 only (T5-XXL's d_kv), any Sq, Skv >= 1; leading dimensions multiples of 8 and 16-byte aligned pointers; anything else returns -22. */
+int tb_attention_rel_fwd(const tb_attn_desc* d, const float* rel, const int32_t* kv_len, tb_stream_t stream);
+/* tb_gated_gelu_tanh: out[m, f] = gelu_new(hg[m, f]) * hg[m, F + f] in fp32, gelu_new(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))).
+ * hg TB_F16 [M, 2F] (the stacked [wi_0 ; wi_1] projection), out TB_F16 [M, F]. */
+int tb_gated_gelu_tanh(const void* hg, int64_t ldh, void* out, int64_t ldo, int64_t M, int F, tb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,9 @@ _SIGS = {
     "tb_img_pack_rgb": ([_VP, _VP, _I64, _VP], C.c_int),
     "tb_img_unpack_rgb": ([_VP, _I64, _I, _I, _VP, _VP], C.c_int),
     "tb_clip_patch_embed": ([_VP, _I64, _I64, _I, _I, _I, _VP, _I64, _I, _VP, _VP, _VP, _VP, _I64, _I, _VP], C.c_int),
+    "tb_rmsnorm_fwd": ([_VP, _I64, _VP, _I64, _I, _VP, _I64, _I, _F, _VP], C.c_int),
+    "tb_attention_rel_fwd": ([C.POINTER(AttnDesc), _VP, _VP, _VP], C.c_int),
+    "tb_gated_gelu_tanh": ([_VP, _I64, _VP, _I64, _I64, _I, _VP], C.c_int),
 }
 IMG_LANCZOS, IMG_BICUBIC = 1, 3
 IMG_BILINEAR = 16   # not Pillow's 2: see TB_IMG_BILINEAR

@@ -946,3 +946,37 @@ def clip_patch_embed(images, patch, w_packed, bias, cls, pos, out):
                                             w_packed.shape[1], L.ptr(bias), L.ptr(cls), L.ptr(pos), L.ptr(out), out.stride(0), D, L.stream()),
                 "tb_clip_patch_embed")
     return out
+
+
+# ------------------------------------------------------------------ T5 (csrc/t5.hip; the VQA score's encoder-decoder, vqa_score.py)
+def rmsnorm_fwd(x, y, gamma, eps=1e-6):
+    """T5LayerNorm: y = x * rsqrt(mean(x^2) + eps) * gamma.  x fp32 [M, C] (rows may be strided), y 16-bit or fp32, gamma fp32 [C]."""
+    M, Cc = y.shape
+    assert x.dtype == torch.float32 and gamma.dtype == torch.float32 and x.stride(1) == 1 and y.stride(1) == 1 and gamma.numel() == Cc
+    with _rec("rmsnorm_kernel", 0.0, float(M * Cc * (x.element_size() + y.element_size()))):
+        L.check(L.lib().tb_rmsnorm_fwd(L.ptr(x), x.stride(0), L.ptr(y), y.stride(0), _dt(y), L.ptr(gamma), M, Cc, eps, L.stream()),
+                "tb_rmsnorm_fwd")
+    return y
+
+
+def attention_rel_fwd(q, k, v, o, lse, B, H, Sq, Skv, hd, rel=None, kv_len=None, scale=1.0, causal=False):
+    """attention_fwd's layout with T5's relative-position bias rel fp32 [H, Sq + Skv - 1] (bias of query i, key j = rel[h, j - i + Sq - 1]) and
+    the key-padding lengths kv_len int32 [B]; either may be None, and so may lse.  hd = 64 only."""
+    d = _attn_desc(q, k, v, o, lse, B, H, Sq, Skv, hd, scale, causal)
+    assert q.dtype == L.half_dtype(), f"{q.dtype} operand but the active library computes in {L.half_kind()}"
+    if rel is not None:
+        assert rel.dtype == torch.float32 and rel.is_contiguous() and tuple(rel.shape) == (H, Sq + Skv - 1), (rel.shape, H, Sq, Skv)
+    if kv_len is not None:
+        assert kv_len.dtype == torch.int32 and kv_len.is_contiguous() and kv_len.numel() == B
+    with _rec("attn_rel_kernel", 4.0 * B * H * Sq * Skv * hd):
+        L.check(L.lib().tb_attention_rel_fwd(d, L.ptr(rel), L.ptr(kv_len), L.stream()), "tb_attention_rel_fwd")
+    return o
+
+
+def gated_gelu_tanh(hg, out):
+    """out[M, F] = gelu_new(hg[:, :F]) * hg[:, F:] (16-bit in, fp32 arithmetic, 16-bit out): T5's gated tanh-GELU on the stacked [wi_0 ; wi_1] GEMM"""
+    M, F = out.shape
+    assert _dt(hg) == L.TB_F16 and _dt(out) == L.TB_F16 and hg.shape[1] == 2 * F and hg.stride(1) == 1 and out.stride(1) == 1
+    with _rec("gated_gelu_kernel", 0.0, float(M * F * 3 * 2)):
+        L.check(L.lib().tb_gated_gelu_tanh(L.ptr(hg), hg.stride(0), L.ptr(out), out.stride(0), M, F, L.stream()), "tb_gated_gelu_tanh")
+    return out

@@ -103,9 +103,8 @@ class HipViT:
             self._bufs = {B: b}   # one batch size at a time: the evaluation encodes full batches and one ragged tail
         return b
 
-    def encode(self, images: torch.Tensor) -> torch.Tensor:
-        """images: int32 RGBX [B, S, S] (S = image_size; rows and images may be strided) -> fp32 [B, out_dim]: the CLS rows after the final
-        LayerNorm, projected (unnormalised) where the tower has a projection"""
+    def _blocks(self, images: torch.Tensor, n_layers: int):
+        """patch embedding, pre-LayerNorm and the first `n_layers` blocks -> (the fp32 residual stream [B * T, D], this batch size's buffers)"""
         g = self.geo
         B, S, S2 = images.shape
         if S != g.image_size or S2 != g.image_size:
@@ -117,7 +116,7 @@ class HipViT:
         ops.clip_patch_embed(images, g.patch_size, self.patch_w, self.patch_b, self.cls, self.pos, e)
         if self.pre_ln is not None:
             ops.layernorm_fwd(e, h, *self.pre_ln, ls, g.eps)
-        for W in self.layers:
+        for W in self.layers[:n_layers]:
             ops.layernorm_fwd(h, x, W["ln1.w"], W["ln1.b"], ls, g.eps)
             ops.gemm(x, W["qkv.w"], qkv, bias=W["qkv.b"])
             ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], o, lse, B, H, T, T, D // H, causal=False)
@@ -125,6 +124,22 @@ class HipViT:
             ops.layernorm_fwd(h2, x, W["ln2.w"], W["ln2.b"], ls, g.eps)
             ops.gemm(x, W["fc1.w"], a, bias=W["fc1.b"], act=self.act)
             ops.gemm(a, W["fc2.w"], h, bias=W["fc2.b"], R=h2, col_scale=W["ls2"])        # x + [ls2 *] mlp
+        return h, bf
+
+    def hidden_states(self, images: torch.Tensor, n_layers: int) -> torch.Tensor:
+        """images as for `encode` -> the fp32 residual stream [B, T, D] after the first `n_layers` blocks (n_layers = num_layers - 1: the
+        penultimate layer LLaVA-style projectors read).  A view of the tower's buffer: the next call overwrites it."""
+        if not 0 <= n_layers <= len(self.layers):
+            raise ValueError(f"n_layers = {n_layers}, the tower has {len(self.layers)} blocks")
+        h, _ = self._blocks(images, n_layers)
+        return h.view(images.shape[0], self.tokens, self.geo.hidden_size)
+
+    def encode(self, images: torch.Tensor) -> torch.Tensor:
+        """images: int32 RGBX [B, S, S] (S = image_size; rows and images may be strided) -> fp32 [B, out_dim]: the CLS rows after the final
+        LayerNorm, projected (unnormalised) where the tower has a projection"""
+        g = self.geo
+        h, bf = self._blocks(images, len(self.layers))
+        B, T, D = images.shape[0], self.tokens, g.hidden_size
         cls_rows = h.as_strided((B, D), (T * D, 1))                                       # the CLS row of every image
         out = torch.empty(B, self.out_dim, device=self.dev, dtype=torch.float32)
         y = out if self.proj is None else bf["cls"]
