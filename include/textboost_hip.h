@@ -390,6 +390,19 @@ int tb_lora_bwd_chain(const void* dY, int64_t lddy, const void* x, int64_t ldx, 
                       float scaling, const void* pend_x, int64_t pend_ldx, const void* pend_dt, int64_t pend_lddt,
                       float* pend_dA /* += */, int da_now, tb_stream_t stream);
 int tb_lora_set_variant(int v);   /* profiling: 0 = the dt slabs of tb_lora_bwd load dY in loops, 1 (default) = all loads up front; returns the old value */
+/* Ranks 9 .. 64 (csrc/lora_wide.hip).  Adapter p owns columns [p*rp, p*rp + r) of t / dt: rp >= r, a multiple of 32, at most 64; Rp >= P*rp is
+   the total width (the callers round it to the GEMM's K granularity); padding columns / rows are zero.  One launch packs `layers` stacked
+   adapters, in `dtype` (TB_F16: the build's 16-bit type, TB_F32: the fp32 mode):
+     a_pad [layers][Rp, K]: A, the down projection's weight          w2_fwd   [layers][P*D, Rp]: block-diagonal scaling * B
+     w2_t  [layers][Rp, P*D]: w2_fwd transposed (may be null)        w2_dgrad [layers][K, Rp]:   A^T */
+int tb_lora_wide_pack(const float* A, const float* Bcat, void* a_pad, void* w2_fwd, void* w2_t, void* w2_dgrad, int dtype, int D, int K,
+                      int r, int rp, int Rp, int P, int layers, float scaling, tb_stream_t stream);
+/* both adapter weight gradients of one layer in one launch, on the matrix cores, fp32 accumulation over all M rows in a fixed order:
+     dB[(p*D + n)*r + j] += scaling * sum_m dY[m, p*D + n] * t[m, p*rp + j]        dA[(p*r + j)*K + k] += sum_m dt[m, p*rp + j] * x[m, k]
+   dY [M, P*D], x [M, K], t / dt [M, >= P*rp] in the 16-bit type; D % 32 == 0, K % 32 == 0, leading dimensions % 8 == 0, 16-byte aligned bases */
+int tb_lora_wide_wgrad(const void* dY, int64_t lddy, const void* x, int64_t ldx, const void* t, int64_t ldt, const void* dt, int64_t lddt,
+                       float* dA /* += */, float* dB /* += */, int64_t M, int D, int K, int r, int rp, int P, float scaling,
+                       tb_stream_t stream);
 
 /* ---- optimizer tail: all scalars stay on the device in `state` (fp32[TB_ST_COUNT]) ------------------- */
 enum { TB_ST_LOSS_SCALE = 0, TB_ST_GROWTH_TRACKER = 1, TB_ST_STEP = 2, TB_ST_FOUND_INF = 3, TB_ST_COEF_LORA = 4,

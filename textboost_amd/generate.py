@@ -118,6 +118,9 @@ def seeded_latent(seed: int, size: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ reader of a trained output directory
+MAX_LORA_RANK = 64   # ops.LORA_MAX_RANK (not imported: reading a run directory needs no kernel library)
+
+
 @dataclass
 class TrainedRun:
     path: str
@@ -144,6 +147,8 @@ def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedR
         raise NotImplementedError(f"{te_dir}: use_rslora adapters are not built (scaling alpha / sqrt(r))")
     if r and cfg.get("lora_alpha", r) != r:
         raise NotImplementedError(f"{te_dir}: lora_alpha = {cfg.get('lora_alpha')} != r = {r}: the kernels carry no separate LoRA scaling")
+    if r > MAX_LORA_RANK:
+        raise NotImplementedError(f"{te_dir}: rank-{r} adapters are not built (the text-encoder adapter kernels take r <= {MAX_LORA_RANK})")
     targets = cfg.get("target_modules") or []
     targets = [targets] if isinstance(targets, str) else list(targets)
     if r and sorted(targets) != sorted(LORA_TARGETS):

@@ -745,13 +745,51 @@ def kv_lora_pack(B, col_base, w2, r, scaling=1.0):
             "tb_kv_lora_pack_f32")
 
 
+LORA_NARROW_MAX = 8    # ranks up to here run the VALU adapter kernels of csrc/text_small.hip; above, the wide layout of csrc/lora_wide.hip
+LORA_MAX_RANK = 64
+
+
+def lora_wide_dims(r, P=3):
+    """(rp, Rp) of the wide layout: adapter p owns columns [p*rp, p*rp + r) of t / dt, rp = r rounded up to the 32-wide MFMA tile; the total
+    width Rp = P*rp rounded up to the GEMM's K granularity (64)."""
+    assert LORA_NARROW_MAX < r <= LORA_MAX_RANK, r
+    rp = (r + 31) // 32 * 32
+    return rp, (P * rp + 63) // 64 * 64
+
+
+def lora_wide_pack(A, Bcat, a_pad, w2_fwd, w2_t, w2_dgrad, D, K, r, rp, P, scaling=1.0, layers=1):
+    """tb_lora_wide_pack: a_pad [layers][Rp, K], w2_fwd [layers][P*D, Rp], w2_t [layers][Rp, P*D] (or None), w2_dgrad [layers][K, Rp] from the
+    fp32 masters A [layers][P*r, K], Bcat [layers][P*D, r]; the outputs' dtype selects the 16-bit or the fp32 form."""
+    Rp = w2_fwd.shape[-1]
+    for o in (a_pad, w2_fwd, w2_dgrad) + (() if w2_t is None else (w2_t,)):
+        assert o.is_contiguous() and o.dtype == w2_fwd.dtype
+    assert a_pad.numel() == layers * Rp * K and w2_fwd.numel() == layers * P * D * Rp and w2_dgrad.numel() == layers * K * Rp
+    assert w2_t is None or w2_t.numel() == w2_fwd.numel()
+    assert A.is_contiguous() and Bcat.is_contiguous() and A.numel() == layers * P * r * K and Bcat.numel() == layers * P * D * r
+    L.check(L.lib().tb_lora_wide_pack(L.ptr(A), L.ptr(Bcat), L.ptr(a_pad), L.ptr(w2_fwd), L.ptr(w2_t), L.ptr(w2_dgrad), _dt(w2_fwd), D, K, r, rp,
+                                      Rp, P, layers, scaling, L.stream()), "tb_lora_wide_pack")
+
+
+def lora_wide_wgrad(dY, x, t, dt, dA, dB, D, K, r, rp, P, scaling=1.0):
+    """tb_lora_wide_wgrad: dB += scaling * dY_p^T t_p, dA += dt_p^T x for the P adapters of one layer (16-bit operands, fp32 gradients)."""
+    M = x.shape[0]
+    assert dY.shape[0] == M and t.shape[0] == M and dt.shape[0] == M and dY.shape[1] == P * D and x.shape[1] == K
+    assert dA.is_contiguous() and dB.is_contiguous() and dA.numel() == P * r * K and dB.numel() == P * D * r
+    assert dA.dtype == torch.float32 and dB.dtype == torch.float32
+    for o in (dY, x, t, dt):
+        assert _dt(o) == L.TB_F16 and o.stride(1) == 1
+    L.check(L.lib().tb_lora_wide_wgrad(L.ptr(dY), dY.stride(0), L.ptr(x), x.stride(0), L.ptr(t), t.stride(0), L.ptr(dt), dt.stride(0), L.ptr(dA),
+                                       L.ptr(dB), M, D, K, r, rp, P, scaling, L.stream()), "tb_lora_wide_wgrad")
+
+
 _lora_ws = {}
 
 
-def lora_bwd(dY, x, t, Bcat, dt, dA, dB, D, K, r, P, scaling=1.0, ws=None, w2_fwd=None, pending=None, defer_da=False):
+def lora_bwd(dY, x, t, Bcat, dt, dA, dB, D, K, r, P, scaling=1.0, ws=None, w2_fwd=None, pending=None, defer_da=False, rp=None):
     """pending / defer_da (16-bit modes): the chained form, tb_lora_bwd_chain -- `pending` = the (x, dt, dA) this function returned for the previous
     adapter set (its dA panels ride in this set's dt / dB launch), defer_da=True returns this set's (x, dt, dA) instead of launching its dA
-    panels; the caller hands it to the next call (dt buffers of consecutive links must differ) or finishes it with lora_bwd_finish."""
+    panels; the caller hands it to the next call (dt buffers of consecutive links must differ) or finishes it with lora_bwd_finish.
+    rp (fp32 mode only): the wide layout, adapter p's columns of t / dt start at p*rp instead of p*r (`lora_wide_dims`)."""
     M = x.shape[0]
     if dY.dtype == torch.float32:
         assert pending is None and not defer_da
@@ -760,12 +798,18 @@ def lora_bwd(dY, x, t, Bcat, dt, dA, dB, D, K, r, P, scaling=1.0, ws=None, w2_fw
         #   (c) dA += dt[:, :P*r]^T @ x
         gemm_f32_t(dY, w2_fwd, dt, M, dt.shape[1], P * D, w_trans=True)
         dBv = dB.view(P * D, r)
+        cs = r if rp is None else rp
         for p in range(P):
-            gemm_f32_t(dY[:, p * D:(p + 1) * D], t[:, p * r:(p + 1) * r], dBv[p * D:(p + 1) * D], D, r, M, a_trans=True, w_trans=True,
+            gemm_f32_t(dY[:, p * D:(p + 1) * D], t[:, p * cs:p * cs + r], dBv[p * D:(p + 1) * D], D, r, M, a_trans=True, w_trans=True,
                        R=dBv[p * D:(p + 1) * D], alpha=scaling)
         dAv = dA.view(P * r, K)
-        gemm_f32_t(dt, x, dAv, P * r, K, M, a_trans=True, w_trans=True, R=dAv)
+        if rp is None:
+            gemm_f32_t(dt, x, dAv, P * r, K, M, a_trans=True, w_trans=True, R=dAv)
+        else:   # (c) per adapter: its r columns of dt are not adjacent to the next adapter's
+            for p in range(P):
+                gemm_f32_t(dt[:, p * rp:p * rp + r], x, dAv[p * r:(p + 1) * r], r, K, M, a_trans=True, w_trans=True, R=dAv[p * r:(p + 1) * r])
         return
+    assert rp is None
     if pending is not None or defer_da:
         px, pdt, pdA = pending if pending is not None else (None, None, None)
         assert pending is None or px.shape == x.shape      # (a pending dt that IS this link's dt: refused by the library)

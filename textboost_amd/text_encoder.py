@@ -94,6 +94,9 @@ class HipTextEncoder:
         self.use_fixed_special_embedding = False
         self.first_added = self.token_table.shape[0]
         self.n_added = 0
+        self.wide = False
+        if self.r > ops.LORA_MAX_RANK:
+            raise NotImplementedError(f"text-encoder LoRA rank {self.r}: ranks up to {ops.LORA_MAX_RANK} are supported")
         if self.r:
             g = torch.Generator(device="cpu")
             if seed is not None:
@@ -103,8 +106,16 @@ class HipTextEncoder:
             self.lora_B = torch.zeros(Lr, 3 * D, self.r, device=device)
             self.grad_A = torch.zeros_like(self.lora_A)
             self.grad_B = torch.zeros_like(self.lora_B)
-            self.w2_fwd = torch.zeros(Lr, 3 * D, 64, device=device, dtype=odt)
-            self.w2_dgrad = torch.zeros(Lr, D, 64, device=device, dtype=odt)
+            # ranks <= 8: the VALU adapter kernels on a 64-column K-extension; above: the wide layout (csrc/lora_wide.hip), adapter p in columns
+            # [p*rp, p*rp + r) of a [*, lw] extension, the down projection / dt as GEMMs and the weight gradients on the matrix cores
+            self.wide = self.r > ops.LORA_NARROW_MAX
+            self.rp, self.lw = ops.lora_wide_dims(self.r) if self.wide else (self.r, 64)
+            self.w2_fwd = torch.zeros(Lr, 3 * D, self.lw, device=device, dtype=odt)
+            self.w2_dgrad = torch.zeros(Lr, D, self.lw, device=device, dtype=odt)
+            if self.wide:
+                self.a_pad = torch.zeros(Lr, self.lw, D, device=device, dtype=odt)
+                # weight of the dt GEMM; the fp32 mode multiplies by w2_fwd through a transposed view instead
+                self.w2_t = None if mode == "fp32" else torch.zeros(Lr, self.lw, 3 * D, device=device, dtype=odt)
 
     # ------------------------------------------------------------------ reference-facing surface
     def set_null_embedding(self, null):  # text_encoder.py:28-32
@@ -149,6 +160,10 @@ class HipTextEncoder:
             return
         D = self.geo.hidden_size
         assert self.lora_A.is_contiguous() and self.lora_B.is_contiguous()
+        if self.wide:
+            ops.lora_wide_pack(self.lora_A, self.lora_B, self.a_pad, self.w2_fwd, self.w2_t, self.w2_dgrad, D, D, self.r, self.rp, 3, self.scaling,
+                               layers=self.geo.num_layers)
+            return
         ops.lora_pack(self.lora_A, self.lora_B, self.w2_fwd, self.w2_dgrad, D, D, self.r, 3, self.scaling, layers=self.geo.num_layers)
 
     # ------------------------------------------------------------------ forward
@@ -180,8 +195,11 @@ class HipTextEncoder:
             ls1 = self.buf(p + "ls1", M, 2, f32)
             qkv = self.buf(p + "qkv", M, 3 * D, f16)
             if self.r:
-                t = self.buf(p + "t", M, 64, f16)  # columns >= 3r (and the frozen extra rows) stay zero (K-extension operand of the qkv GEMM)
-                if full32:  # no fused (fp16) down projection: t[:Ms, :3r] = x1 @ A^T as an exact-fp32 GEMM
+                t = self.buf(p + "t", M, self.lw, f16)  # columns >= 3r (and the frozen extra rows) stay zero (K-extension operand of the qkv GEMM)
+                if self.wide:  # t[:Ms] = x1 @ a_pad^T: the padded weight's zero rows write the padding columns' zeros
+                    ops.layernorm_fwd(h, x1, W["ln1.g"], W["ln1.b"], ls1, geo.eps)
+                    ops.gemm(x1[:Ms], self.a_pad[i], t[:Ms])
+                elif full32:  # no fused (fp16) down projection: t[:Ms, :3r] = x1 @ A^T as an exact-fp32 GEMM
                     ops.layernorm_fwd(h, x1, W["ln1.g"], W["ln1.b"], ls1, geo.eps)
                     ops.gemm(x1[:Ms], self.lora_A[i], t[:Ms, :3 * self.r])
                 else:
@@ -270,7 +288,15 @@ class HipTextEncoder:
                               dqkv[:, 2 * D:], B, H, T, T, hd, causal=True)
             dx1 = self.buf(gs + "dx", M, D, f16)
             if self.r:
-                if full32 or not CHAIN_LORA_BWD:
+                if self.wide:
+                    dt = self.buf(gs + "dt", M, self.lw, f16)
+                    if full32:
+                        ops.lora_bwd(dqkv, x1, self._bufs[p + "t"][:M], self.lora_B[i], dt, grad_A[i], grad_B[i], D, D, self.r, 3, self.scaling,
+                                     w2_fwd=self.w2_fwd[i], rp=self.rp)
+                    else:
+                        ops.gemm(dqkv, self.w2_t[i], dt)
+                        ops.lora_wide_wgrad(dqkv, x1, self._bufs[p + "t"][:M], dt, grad_A[i], grad_B[i], D, D, self.r, self.rp, 3, self.scaling)
+                elif full32 or not CHAIN_LORA_BWD:
                     dt = self.buf(gs + "dt", M, 64, f16)
                     ops.lora_bwd(dqkv, x1, self._bufs[p + "t"][:M], self.lora_B[i], dt, grad_A[i], grad_B[i], D, D, self.r, 3,
                                  self.scaling, w2_fwd=self.w2_fwd[i])

@@ -333,6 +333,8 @@ def _train_subject(ctx, args, final, fh, val_ids):
     fp32_mode = args.mixed_precision in (None, "no")
     bf16_mode = args.mixed_precision == "bf16"
     te_mode = "fp32" if fp32_mode else "autocast"
+    if args.lora_rank > 64:   # (checked here, with the other options that still raise further down, before the encoder allocates for the rank)
+        raise NotImplementedError(f"--lora_rank {args.lora_rank}: the text-encoder adapter kernels take ranks up to 64")
     te = HipTextEncoder(clip_geo, ctx.csd, B, mode=te_mode, lora_rank=args.lora_rank, n_slots=1, device=dev, seed=args.seed)
     if final:
         ctx.csd = None
