@@ -300,6 +300,13 @@ int tb_attention_bwd(const tb_attn_desc* d, tb_stream_t stream);
  * short key sequences (cross-attention on the prompt, 33 .. 96 keys, otherwise attn_xs_fwd_kernel / attn_xs_bwd_dq_kernel), 32768 = the query-split dK / dV launch of short key sequences cuts until 1024 (not 512)
  * workgroups exist; returns the previous value */
 int tb_attention_set_variant(int bits);
+/* Token attention maps (csrc/attn_maps.hip): the probabilities of a cross-attention the flash forward never materialises, summed over heads,
+ *   maps[b - b0][j][s] (+)= w * sum_h softmax_j(scale * q_{b,h,s} . k_{b,h,j})     for b in [b0, b0 + nb), fp32 [nb, Skv, Sq]
+ * so every key (prompt token) j owns one contiguous image over the queries.  Reads B, H, Sq, Skv, hd, scale, Q / ldq and K / ldk of the
+ * descriptor (the layout of tb_attention_fwd; any ldq, ldk >= H * hd); the softmax is the kernel's own, not the forward's LSE.  dtype is the
+ * operands' (TB_F16 only).  accumulate = 0 overwrites `maps`, 1 adds to it (no atomics: each element has one owner, so a launch is
+ * bit-reproducible).  hd % 8 == 0, hd <= 160, 1 <= Skv <= 128, any Sq; anything else returns -22 and launches nothing. */
+int tb_attn_token_maps(const tb_attn_desc* d, int dtype, int b0, int nb, float w, int accumulate, float* maps, tb_stream_t stream);
 
 /* ---- scheduler / boundary / loss / misc streaming kernels ------------------------------------------ */
 /* noise_scheduler.add_noise (:1052) [+ get_velocity (:1073) when velocity != NULL]; fp32 NCHW in, fp16 noisy out */

@@ -10,6 +10,12 @@ textboost_amd/generate.py.
 50 steps at guidance 7.5 with DPM-Solver++.  With --output the images form one grid (1 x len(seeds)); without it each is written to
 `<prompt with _ for spaces>_<seed>.jpg` in the working directory.
 
+--attn-map [WORD ...] also writes where each word lands in the images (textboost_amd/attn_maps.py: the UNet's cross-attention from image
+positions to prompt tokens, averaged over heads, layers and steps of the conditional half): `<output stem>_attn.jpg`, one row of overlays per
+word and one column per seed, and `<output stem>_attn.npz` with `maps` fp32 [seeds, words, h, w], `words` and `seeds`; without --output one
+`<prompt>_<seed>_attn.jpg` / `.npz` pair per seed.  Without a word the run's placeholder tokens that occur in the prompt are taken.  The images
+themselves do not change.
+
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
 latent of a seed is drawn on the CPU (textboost_amd.generate.seeded_latent), the same on every machine."""
@@ -35,7 +41,56 @@ def build_parser():
     p.add_argument("--seeds", type=int, nargs="+", default=[0, 1, 2, 3])
     p.add_argument("--output", type=str, default=None)
     p.add_argument("--steps", type=int, default=50, help="sampling steps (the pipeline's default)")
+    p.add_argument("--attn-map", dest="attn_map", type=str, nargs="*", default=None, metavar="WORD",
+                   help="also write token attention maps of these words of the prompt (no word: the run's placeholder tokens in the prompt)")
     return p
+
+
+def attn_map_words(model_dir, run, prompt, requested):
+    """--attn-map: (words, their token positions in the tokenised prompt), on the host.  No word: the run's placeholder tokens that occur in the
+    prompt.  A word that does not occur is a SystemExit."""
+    import json
+    from textboost_amd.attn_maps import run_tokenizer, token_positions
+    tokenizer = run_tokenizer(model_dir, run)
+    T = 77
+    cfg = os.path.join(model_dir, "text_encoder", "config.json")
+    if os.path.exists(cfg):
+        with open(cfg) as f:
+            T = json.load(f).get("max_position_embeddings", 77)
+    words, positions = [], []
+    if requested:
+        for w in requested:
+            try:
+                positions.append(token_positions(tokenizer, prompt, w, T))
+            except ValueError as e:
+                raise SystemExit(f"inference.py: --attn-map: {e}")
+            words.append(w)
+        return words, positions
+    for w, _ in run.tokens:
+        try:
+            positions.append(token_positions(tokenizer, prompt, w, T))
+        except ValueError:
+            continue
+        words.append(w)
+    if not words:
+        raise SystemExit(f"inference.py: --attn-map: none of the run's tokens {[n for n, _ in run.tokens]} occurs in {prompt!r}; name the words")
+    return words, positions
+
+
+def write_attn_maps(stem, images, word_maps, words, seeds):
+    """`<stem>.jpg`: overlays, one row per word and one column per seed; `<stem>.npz`: maps fp32 [seeds, words, h, w], words, seeds"""
+    import numpy as np
+    from PIL import Image
+    from textboost_amd.attn_maps import overlay
+    W, H = images[0].size
+    sheet = Image.new("RGB", (len(images) * W, len(words) * H))
+    for k, im in enumerate(images):
+        rgb = np.asarray(im)
+        for j in range(len(words)):
+            sheet.paste(Image.fromarray(overlay(rgb, word_maps[k, j])), box=(k * W, j * H))
+    sheet.save(stem + ".jpg")
+    np.savez(stem + ".npz", maps=np.asarray(word_maps, dtype=np.float32), words=np.array(list(words)), seeds=np.array(list(seeds), dtype=np.int64))
+    print(f"wrote {stem}.jpg and {stem}.npz")
 
 
 def main(argv=None):
@@ -48,6 +103,9 @@ def main(argv=None):
     if args.checkpoint is not None:
         path = os.path.join(path, f"checkpoint-{args.checkpoint}")
     run = G.read_run_dir(path)
+    words = positions = None
+    if args.attn_map is not None:        # every refusal before anything reaches the device
+        words, positions = attn_map_words(args.model, run, args.prompt, args.attn_map)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("inference.py needs an MI355X: the product path has no CPU fallback")
@@ -61,20 +119,34 @@ def main(argv=None):
         ids = G.tokenize(tokenizer, [""] * n + [args.prompt] * n, T).to(pipe.dev)
         states = te.forward(ids, pins=False).view(2, n * T, -1)
         latents = torch.cat([G.seeded_latent(s, pipe.size) for s in args.seeds]).to(pipe.dev)
-        rgbx = pipe.images(states[1], states[0], latents, what=f"prompt {args.prompt!r}, seeds {args.seeds}")
+        recorder = None
+        if words is not None:
+            from textboost_amd.attn_maps import AttnMapRecorder
+            recorder = AttnMapRecorder(pipe.unet)
+        rgbx = pipe.images(states[1], states[0], latents, what=f"prompt {args.prompt!r}, seeds {args.seeds}", maps=recorder)
         from PIL import Image
         images = [Image.fromarray(augment.to_host_rgb(rgbx[k])) for k in range(n)]
+        word_maps = None
+        if recorder is not None:
+            from textboost_amd.attn_maps import word_map
+            token_maps = recorder.result()                                                  # [n, T, h, w]
+            word_maps = torch.stack([word_map(token_maps, p) for p in positions], dim=1).cpu().numpy()     # [n, words, h, w]
     if args.output is not None:
         grid = Image.new("RGB", (n * images[0].width, images[0].height))     # diffusers.utils.make_image_grid(images, 1, n)
         for k, im in enumerate(images):
             grid.paste(im, box=(k * im.width, 0))
         grid.save(args.output)
         print(f"wrote {args.output}")
+        if word_maps is not None:
+            write_attn_maps(os.path.splitext(args.output)[0] + "_attn", images, word_maps, words, args.seeds)
     else:
         for seed, im in zip(args.seeds, images):
             out = args.prompt.replace(" ", "_") + f"_{seed}.jpg"
             im.save(out)
             print(f"wrote {out}")
+        if word_maps is not None:
+            for k, seed in enumerate(args.seeds):
+                write_attn_maps(args.prompt.replace(" ", "_") + f"_{seed}_attn", images[k:k + 1], word_maps[k:k + 1], words, [seed])
 
 
 if __name__ == "__main__":

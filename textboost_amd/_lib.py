@@ -156,6 +156,7 @@ _SIGS = {
     "tb_layernorm_bwd": ([_VP, _I64, _I, _VP, _I64, _I, _VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _I64, _I, _VP], C.c_int),
     "tb_attention_fwd": ([C.POINTER(AttnDesc), _VP], C.c_int),
     "tb_attention_bwd": ([C.POINTER(AttnDesc), _VP], C.c_int),
+    "tb_attn_token_maps": ([C.POINTER(AttnDesc), _I, _I, _I, _F, _I, _VP, _VP], C.c_int),
     "tb_add_noise": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I64, _VP], C.c_int),
     "tb_timestep_embed": ([_VP, _VP, _I, _I, _VP], C.c_int),
     "tb_conv4_to_nhwc": ([_VP, _I, _VP, _VP, _VP, _I64, _I, _I, _I, _I, _I, _F, _VP], C.c_int),

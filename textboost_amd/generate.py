@@ -290,10 +290,11 @@ class Pipeline:
         return cls(models.unet_geometry_from_config(ucfg), usd, vgeo, vsd, scfg, int(ucfg.get("sample_size", 64)), batch, steps, guidance,
                    text_len=text_len, device=device)
 
-    def images(self, cond, uncond, latents, what: str = "") -> torch.Tensor:
+    def images(self, cond, uncond, latents, what: str = "", maps=None) -> torch.Tensor:
         """text states fp32 [B*T, D] twice, latents fp32 [B, 4, size, size] on the device -> int32 RGBX [B, 8 size, 8 size] (resident).
-        Non-finite final latents raise before anything is decoded."""
-        x = self.sampler.denoise(cond, uncond, latents=latents)
+        Non-finite final latents raise before anything is decoded.  maps: an `attn_maps.AttnMapRecorder` of `self.unet` (the images do not
+        change with it)."""
+        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps)
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         return self.vae.decode_rgbx(x)

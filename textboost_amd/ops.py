@@ -468,6 +468,21 @@ def attention_bwd(q, k, v, o, lse, do, delta, dq, dk, dv, B, H, Sq, Skv, hd, sca
         L.check(L.lib().tb_attention_bwd(d, L.stream()), "tb_attention_bwd")
 
 
+def attn_token_maps(q, k, maps, B, H, Sq, Skv, hd, scale=None, b0=0, nb=None, w=1.0, accumulate=False):
+    """maps[b - b0, j, s] (+)= w * sum_h softmax_j(scale q_{b,h,s} . k_{b,h,j}) for the images [b0, b0 + nb): q [B*Sq, H*hd], k [B*Skv, H*hd] in
+    the library's half type (column slices allowed), maps fp32 [nb, Skv, Sq] contiguous (csrc/attn_maps.hip; Skv <= 128)."""
+    nb = B - b0 if nb is None else nb
+    assert maps.dtype == torch.float32 and maps.is_contiguous() and maps.numel() == nb * Skv * Sq, (maps.dtype, tuple(maps.shape), nb, Skv, Sq)
+    assert q.dtype == k.dtype and q.stride(1) == 1 and k.stride(1) == 1
+    d = L.AttnDesc()
+    d.B, d.H, d.Sq, d.Skv, d.hd, d.causal, d.scale = B, H, Sq, Skv, hd, 0, scale if scale is not None else hd ** -0.5
+    d.Q, d.ldq = L.ptr(q), q.stride(0)
+    d.K, d.ldk = L.ptr(k), k.stride(0)
+    with _rec("attn_token_maps_kernel", 2.0 * nb * H * Sq * Skv * hd):
+        L.check(L.lib().tb_attn_token_maps(d, _dt(q), b0, nb, w, int(accumulate), L.ptr(maps), L.stream()), "tb_attn_token_maps")
+    return maps
+
+
 # ------------------------------------------------------------------ small streaming kernels
 def add_noise(x0, noise, timesteps, acp, noisy, velocity=None):
     B = x0.shape[0]

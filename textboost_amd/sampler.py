@@ -172,10 +172,13 @@ class HipSampler:
         self.t_dev = [torch.full((2 * B,), t, dtype=torch.int64, device=dev) for t in self.timesteps]
         self.generator: Optional[torch.Generator] = None
 
-    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None):
+    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None):
         """cond / uncond: fp16 or fp32 [B*77, D] text-encoder outputs.  Returns the final latents fp32 [B,4,h,w].
-        step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`."""
+        step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`.
+        maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step."""
         B, sch = self.B, self.sch
+        if maps is not None:
+            maps.zero()
         if latents is None:
             latents = torch.randn(self.x.shape, device=self.x.device, generator=self.generator)
         self.x.copy_(latents * sch.init_noise_sigma)
@@ -185,7 +188,7 @@ class HipSampler:
         ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
         n = self.x[0].numel()
         for i in range(self.steps):
-            eps2 = self.unet.forward(self.x2, self.t_dev[i], ehs)
+            eps2 = self._unet_forward(i, ehs, maps)
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i)
             if getattr(sch, "needs_noise", False):  # the variance noise of the ancestral step rides in the m_prev operand
@@ -195,6 +198,15 @@ class HipSampler:
                     self.m_prev.normal_(generator=self.generator)
             ops.dpm_step(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc)
         return self.x
+
+    def _unet_forward(self, i, ehs, maps):
+        if maps is None:
+            return self.unet.forward(self.x2, self.t_dev[i], ehs)
+        prev, self.unet.attn_maps = self.unet.attn_maps, maps
+        try:
+            return self.unet.forward(self.x2, self.t_dev[i], ehs)
+        finally:
+            self.unet.attn_maps = prev
 
     def sample(self, cond_ehs, uncond_ehs, latents=None):
         return self.vae.decode(self.denoise(cond_ehs, uncond_ehs, latents))

@@ -138,6 +138,7 @@ class HipUNet:
         # BASELINE.json configs[4]: e4m3 P.V in the forward of the hd = 40 self-attention layers (opt-in; fp16 everywhere else and in the backward)
         self.attn_fp8 = attn_fp8
         self._fp8_ws = None
+        self.attn_maps = None   # an attn_maps.AttnMapRecorder: every cross-attention forward then also records its token maps (opt-in; None = no launch)
         self._bufs: Dict[str, torch.Tensor] = {}
         self.tape: List = []
         self._pack(state_dict)
@@ -503,6 +504,8 @@ class HipUNet:
         o2 = self.buf(prefix + ".o2", M, C)
         lse2 = self.buf(prefix + ".lse2", B * heads, HW, torch.float32)
         ops.attention_fwd(q2, k2, v2, o2, lse2, B, heads, HW, T, hd)
+        if self.attn_maps is not None:
+            self.attn_maps.record(q2, k2, heads, lvl_hw, hd)
         t2 = self.buf(prefix + ".t2", M, C)
         # --- GEGLU feed-forward
         ls3 = self.buf(prefix + ".ls3", M, 2, torch.float32)
