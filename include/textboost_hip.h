@@ -471,6 +471,13 @@ int tb_optimizer_tail(const tb_opt_desc* d, tb_stream_t stream);
  * weight-gradient-shaped products of the LoRA adapters (dB = dY^T t, dA = dt^T x; train_textboost.py:700-722) */
 int tb_gemm_f32(const tb_gemm_desc* d, tb_stream_t stream);
 int tb_gemm_f32_t(const tb_gemm_desc* d, int a_trans, int w_trans, tb_stream_t stream);
+/* How every fp32 contraction above and below (tb_gemm_f32, tb_gemm_f32_t, the products inside tb_attention_f32_fwd / _bwd) multiplies.
+ * 0 (default) = exact fp32 products.  1 = split: each operand as bf16 hi + bf16 lo, three bf16 matrix products lo*hi + hi*lo + hi*hi with
+ * fp32 accumulation (<= 3 * 2^-18 of |a||w| per product; the trainer's --allow_tf32).  Process-wide, read when a launch is issued: a
+ * captured graph keeps the mode it was captured under.  tb_f32_set_mode returns the previous mode; any other value returns -22 and changes
+ * nothing.  Deterministic in both modes (one owner per output element, fixed order). */
+int tb_f32_set_mode(int mode);
+int tb_f32_get_mode(void);
 /* attention with fp32 Q / K / V / O / dO / dQ / dK / dV (same descriptor; fp8_ws and ws of the descriptor are ignored).  The score matrix is
  * materialised: ws = tb_attention_f32_ws_floats(B, H, Sq, Skv) floats (forward uses the first half) */
 int64_t tb_attention_f32_ws_floats(int B, int H, int Sq, int Skv);

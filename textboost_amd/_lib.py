@@ -200,6 +200,8 @@ _SIGS = {
     "tb_optimizer_tail": ([C.POINTER(OptDesc), _VP], C.c_int),
     "tb_gemm_f32": ([C.POINTER(GemmDesc), _VP], C.c_int),
     "tb_gemm_f32_t": ([C.POINTER(GemmDesc), _I, _I, _VP], C.c_int),
+    "tb_f32_set_mode": ([_I], C.c_int),
+    "tb_f32_get_mode": ([], C.c_int),
     "tb_attention_f32_ws_floats": ([_I, _I, _I, _I], _I64),
     "tb_attention_f32_fwd": ([C.POINTER(AttnDesc), _VP, _I64, _VP], C.c_int),
     "tb_attention_f32_bwd": ([C.POINTER(AttnDesc), _VP, _I64, _VP], C.c_int),
@@ -233,6 +235,9 @@ IMG_LANCZOS, IMG_BICUBIC = 1, 3
 IMG_BILINEAR = 16   # not Pillow's 2: see TB_IMG_BILINEAR
 
 
+F32_EXACT, F32_SPLIT = 0, 1
+_f32_mode = F32_EXACT   # tb_f32_set_mode of EVERY loaded build of the library (and of one loaded later): see set_f32_mode
+
 _half = "fp16"     # the 16-bit float of the ACTIVE library: one process runs one numeric mode (like the reference's accelerator)
 _libs = {}
 
@@ -261,6 +266,26 @@ def use_half(kind: str):
         set_half(prev)
 
 
+def set_f32_mode(mode: int) -> int:
+    """how the fp32 contractions multiply (tb_f32_set_mode): 0 = exact fp32 products, 1 = three bf16 products of split operands.  The mode
+    is a property of the process, not of one build of the library: it is applied to every build that is loaded (`use_half` switches
+    builds around the VAE) and `lib()` applies it to a build it loads later.  Returns the previous mode."""
+    global _f32_mode
+    mode = int(mode)
+    if mode not in (F32_EXACT, F32_SPLIT):
+        raise ValueError(f"f32 mode {mode}: 0 (exact) or 1 (split)")
+    prev, _f32_mode = _f32_mode, mode
+    for h in _libs.values():
+        rc = h.tb_f32_set_mode(mode)
+        if rc < 0:
+            raise RuntimeError(f"tb_f32_set_mode({mode}) failed with code {rc}")
+    return prev
+
+
+def get_f32_mode() -> int:
+    return _f32_mode
+
+
 def half_kind() -> str:
     return _half
 
@@ -283,6 +308,8 @@ def lib():
             fn = getattr(_lib, name)  # AttributeError here = library older than the header
             fn.argtypes, fn.restype = args, res
         _libs[_half] = _lib
+        if _lib.tb_f32_set_mode(_f32_mode) < 0:
+            raise RuntimeError(f"tb_f32_set_mode({_f32_mode}) failed")
     return _lib
 
 

@@ -8,14 +8,31 @@
 // epilogues of the fp16 family) and, batched over (batch, head) with transposed operand views, the four products of attention; the
 // remaining kernels are plain streaming kernels.  The matrix rate of fp32 MFMA is 1/16 of fp16 (157 TFLOP/s peak), the mode is expected
 // to run an order of magnitude below the fp16 one.
+//
+// Split mode (tb_f32_set_mode(1), the trainer's --allow_tf32): the same kernel with another staging / accumulate stage.  gfx950 has no
+// TF32 instruction; every fp32 operand is written as hi + lo with hi = bf16(a), lo = bf16(a - hi) when it is staged into LDS, and a
+// k-block is the three products lo_a hi_w + hi_a lo_w + hi_a hi_w on v_mfma_f32_32x32x16_bf16 (fp32 accumulation, small terms first).
+// Each operand is kept to 2^-18 relative, the dropped lo lo term is <= 2^-18: <= 3 * 2^-18 of |a||w| per product, ~60 x tighter than
+// TF32, at 96 instead of 512 matrix issue cycles per 16-deep k-slice.  Loaders (all gathers, the K-extension, transposed views) and the
+// epilogue are shared with the exact mode; the mode is process-wide, read when a launch is issued, 0 (exact) unless set.
 #include "common.h"
 #include "../../include/textboost_hip.h"
+#include <atomic>
 
 namespace {
 
 constexpr int GB = 64;    // tile: 64 x 64 outputs per 256-thread workgroup (four waves, one 32x32 MFMA accumulator each)
 constexpr int GK = 16;    // k-slice per LDS stage
 constexpr int GLD = 20;   // LDS row pitch (floats): 80 B rows keep the 32-byte fragment reads spread over the banks
+// split mode: four bf16 images (A-hi, A-lo, W-hi, W-lo) of GB rows x GK k.  Row pitch 24 bf16 = 48 B = three 16-byte slots: a lane's fragment
+// (8 consecutive k of its row) is one ds_read_b128 at row * 48 + 16 * (lane >> 5).  That read is served in four groups of 16 lanes
+// ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32); a group's rows are 16 different residues mod 16 and the slot of row r is
+// (3 r + const) mod 16 with 3 odd, so the 16 lanes of a group take the 16 different slots of the 256-byte bank row: conflict-free
+// (checked by enumerating (addr / 4) % 64 over each group for all four wave positions: every bank is hit once).
+constexpr int SLD = 24;
+
+typedef __attribute__((ext_vector_type(4))) __bf16 sbf16x4;   // (named apart from f16x4 / f16x8, which are fp16 in the default build)
+typedef __attribute__((ext_vector_type(8))) __bf16 sbf16x8;
 
 struct GemmExt {  // operand views beyond tb_gemm_desc: transposed operands and a batch of independent problems
   int a_trans, w_trans;      // A given as [K][M] (element (m, k) at k * lda + m); W given as [K][N]
@@ -30,9 +47,25 @@ __device__ __forceinline__ float act_fwd(int act, float v) {
   return v;
 }
 
+// hi = bf16(v) (round to nearest even), lo = bf16(v - hi); lo = 0 where hi is not finite (inf / NaN inputs, and finite inputs that round to
+// inf), so that such a value reaches the products as itself and never as inf - inf
+__device__ __forceinline__ void split_bf16x4(const float* v, sbf16x4& h, sbf16x4& l) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const __bf16 hb = (__bf16)v[e];
+    const float hf = (float)hb;
+    h[e] = hb;
+    l[e] = (__builtin_fabsf(hf) < INFINITY) ? (__bf16)(v[e] - hf) : (__bf16)0.f;
+  }
+}
+
+// SPLIT = false: exact fp32 products (v_mfma_f32_32x32x2_f32).  SPLIT = true: three bf16 products per k-block (see the header).  Only the
+// LDS staging and the accumulate stage differ.
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const tb_gemm_desc p, const GemmExt x) {
-  __shared__ __attribute__((aligned(16))) float As[GB * GLD];
-  __shared__ __attribute__((aligned(16))) float Ws[GB * GLD];
+  __shared__ __attribute__((aligned(16))) float As[SPLIT ? 1 : GB * GLD];
+  __shared__ __attribute__((aligned(16))) float Ws[SPLIT ? 1 : GB * GLD];
+  __shared__ __attribute__((aligned(16))) __bf16 Sp[SPLIT ? 4 * GB * SLD : 1];   // A-hi | A-lo | W-hi | W-lo
   __shared__ __attribute__((aligned(16))) float Cs[GB * (GB + 1)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int wm = wave >> 1, wn = wave & 1;
@@ -137,22 +170,43 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const tb_gemm_desc p, con
   load_w(0, rw);
   for (int64_t k0 = 0; k0 < p.K; k0 += GK) {
     __syncthreads();  // the previous slice's fragment reads are done
-    *(f32x4*)(As + srow * GLD + sk) = f32x4{ra[0], ra[1], ra[2], ra[3]};
-    *(f32x4*)(Ws + srow * GLD + sk) = f32x4{rw[0], rw[1], rw[2], rw[3]};
+    if constexpr (SPLIT) {
+      sbf16x4 ah, al, wh, wl;
+      split_bf16x4(ra, ah, al);
+      split_bf16x4(rw, wh, wl);
+      *(sbf16x4*)(Sp + 0 * GB * SLD + srow * SLD + sk) = ah;
+      *(sbf16x4*)(Sp + 1 * GB * SLD + srow * SLD + sk) = al;
+      *(sbf16x4*)(Sp + 2 * GB * SLD + srow * SLD + sk) = wh;
+      *(sbf16x4*)(Sp + 3 * GB * SLD + srow * SLD + sk) = wl;
+    } else {
+      *(f32x4*)(As + srow * GLD + sk) = f32x4{ra[0], ra[1], ra[2], ra[3]};
+      *(f32x4*)(Ws + srow * GLD + sk) = f32x4{rw[0], rw[1], rw[2], rw[3]};
+    }
     __syncthreads();
     if (k0 + GK < p.K) {  // next slice in flight under the multiplication
       load_a(k0 + GK, ra);
       load_w(k0 + GK, rw);
     }
-    // MFMA j of the slice multiplies k = 8 hi + j (any order both operands agree on): a lane's 8 values are contiguous in its row
-    const float* ap = As + (wm * 32 + l31) * GLD + hi * 8;
-    const float* wp = Ws + (wn * 32 + l31) * GLD + hi * 8;
-    const f32x4 a0 = *(const f32x4*)ap, a1 = *(const f32x4*)(ap + 4);
-    const f32x4 w0 = *(const f32x4*)wp, w1 = *(const f32x4*)(wp + 4);
+    if constexpr (SPLIT) {
+      // operand lane map of 32x32x16_bf16: lane (l31, hi) holds k = 8 hi + j, j = 0..7, of row l31: one 16-byte read per image
+      const __bf16* ap = Sp + (wm * 32 + l31) * SLD + hi * 8;
+      const __bf16* wp = Sp + 2 * GB * SLD + (wn * 32 + l31) * SLD + hi * 8;
+      const sbf16x8 ah = *(const sbf16x8*)ap, al = *(const sbf16x8*)(ap + GB * SLD);
+      const sbf16x8 wh = *(const sbf16x8*)wp, wl = *(const sbf16x8*)(wp + GB * SLD);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wh, acc, 0, 0, 0);   // small terms first
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wl, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wh, acc, 0, 0, 0);
+    } else {
+      // MFMA j of the slice multiplies k = 8 hi + j (any order both operands agree on): a lane's 8 values are contiguous in its row
+      const float* ap = As + (wm * 32 + l31) * GLD + hi * 8;
+      const float* wp = Ws + (wn * 32 + l31) * GLD + hi * 8;
+      const f32x4 a0 = *(const f32x4*)ap, a1 = *(const f32x4*)(ap + 4);
+      const f32x4 w0 = *(const f32x4*)wp, w1 = *(const f32x4*)(wp + 4);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], w0[j], acc, 0, 0, 0);
+      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], w0[j], acc, 0, 0, 0);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], w1[j], acc, 0, 0, 0);
+      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], w1[j], acc, 0, 0, 0);
+    }
   }
   // ---- epilogue through an LDS image of the tile: every global access below is row-contiguous
 #pragma unroll
@@ -216,6 +270,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const tb_gemm_desc p, con
   }
 }
 
+std::atomic<int> g_f32_mode{0};   // 0 = exact fp32 products, 1 = three-term bf16 split (tb_f32_set_mode)
+
 int check_gemm_f32(const tb_gemm_desc& d, const GemmExt& x) {
   if (!d.A || !d.W || !d.C || d.M <= 0 || d.N <= 0 || d.K <= 0) return TB_EINVAL;
   if (d.col_scale) return TB_EINVAL;   // LayerScale lives in the 16-bit path's epilogues only
@@ -244,7 +300,10 @@ int launch_gemm_f32(tb_gemm_desc d, const GemmExt& x, hipStream_t s) {
   const int rc = check_gemm_f32(d, x);
   if (rc) return rc;
   dim3 grid((unsigned)((d.N + GB - 1) / GB), (unsigned)((d.M + GB - 1) / GB), (unsigned)x.batch);
-  hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, s, d, x);
+  if (g_f32_mode.load(std::memory_order_relaxed) == 1)   // read per launch: a captured graph keeps the mode it was captured under
+    hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, dim3(256), 0, s, d, x);
+  else
+    hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, dim3(256), 0, s, d, x);
   TB_CHECK_LAUNCH();
   return TB_OK;
 }
@@ -536,6 +595,11 @@ extern "C" int tb_kv_lora_pack_f32(const float* B, const int32_t* col_base, floa
   TB_CHECK_LAUNCH();
   return TB_OK;
 }
+extern "C" int tb_f32_set_mode(int mode) {
+  if (mode != 0 && mode != 1) return TB_EINVAL;
+  return g_f32_mode.exchange(mode);
+}
+extern "C" int tb_f32_get_mode(void) { return g_f32_mode.load(); }
 extern "C" int tb_gemm_f32(const tb_gemm_desc* dp, tb_stream_t stream) {
   (void)hipGetLastError();
   if (!dp) return TB_EINVAL;

@@ -2,6 +2,7 @@
 Tensors are PyTorch-ROCm tensors used for memory + streams only; all arithmetic happens in the HIP kernels."""
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -307,6 +308,17 @@ def gemm_f32_t(A, W, out, M, N, K, *, a_trans=False, w_trans=False, R=None, alph
     d.C, d.ldc, d.c_dtype = L.ptr(out), out.stride(0), L.TB_F32
     L.check(L.lib().tb_gemm_f32_t(d, int(a_trans), int(w_trans), L.stream()), "tb_gemm_f32_t")
     return out
+
+
+@contextlib.contextmanager
+def f32_mode(mode):
+    """run a block with the fp32 contractions in `mode` (0 = exact, 1 = split bf16: _lib.set_f32_mode) and restore the previous mode.  The mode
+    is read when a launch is issued, so a graph captured inside the block keeps it."""
+    prev = L.set_f32_mode(mode)
+    try:
+        yield
+    finally:
+        L.set_f32_mode(prev)
 
 
 def groupnorm_ws(B, HW, C, G=32):

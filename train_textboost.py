@@ -307,7 +307,35 @@ def release_subject_caches():
     ops.clear_step_workspaces()
 
 
+def requested_f32_mode(args):
+    """--allow_tf32 (:820-821: torch.backends.cuda.matmul.allow_tf32 = True) -> (mode for _lib.set_f32_mode or None, line for training.log or None).
+    gfx950 has no TF32 instruction: in the fp32 mode the flag selects the three-term bf16 split of every fp32 contraction (csrc/f32_path.hip,
+    ~60 x tighter than TF32).  Under --mixed_precision fp16 / bf16 the only fp32 products are the adapters' few exact GEMMs: nothing is set."""
+    if not getattr(args, "allow_tf32", False):
+        return None, None
+    if args.mixed_precision in (None, "no"):
+        return 1, "--allow_tf32: fp32 contractions run in f32 mode 1 (three-term bf16 split on the matrix cores, <= 3 * 2^-18 per product)"
+    return None, (f"--allow_tf32 has no effect under --mixed_precision {args.mixed_precision}: its fp32 products are the adapters' few exact "
+                  "GEMMs (f32 mode 0)")
+
+
 def _train_subject(ctx, args, final, fh, val_ids):
+    """the subject under the f32 mode its arguments ask for: set before the step is built and captured, the previous mode restored afterwards
+    (a resident sweep's next subject without --allow_tf32 is exact again)"""
+    from textboost_amd import _lib as _L
+    mode, line = requested_f32_mode(args)
+    if line is not None and ctx.is_main:
+        logger.info(line)
+    if mode is None:
+        return _train_subject_in_mode(ctx, args, final, fh, val_ids)
+    prev = _L.set_f32_mode(mode)
+    try:
+        return _train_subject_in_mode(ctx, args, final, fh, val_ids)
+    finally:
+        _L.set_f32_mode(prev)
+
+
+def _train_subject_in_mode(ctx, args, final, fh, val_ids):
     t_begin = time.perf_counter()
     spent = {"capture": 0.0, "steps": 0.0, "validation": 0.0, "checkpoints": 0.0}
     world, rank, dev, is_main, clip_geo = ctx.world, ctx.rank, ctx.dev, ctx.is_main, ctx.clip_geo
