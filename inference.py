@@ -3,17 +3,24 @@
 textboost_amd/generate.py.
 
     python inference.py <output_dir> --model <diffusers model dir> --prompt "photo of a <dog> dog" [--seeds 0 1 2 3] [--output grid.jpg]
-        [--checkpoint N]
+        [--checkpoint N] [--with <output_dir> ...] [--weights W ...]
 
-`<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`); the text encoder is the plain CLIP text model
+`<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
+cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
 (no null-embedding pins: the reference's pipeline here holds a `CLIPTextModel`, inference.py:47-52), one latent PER SEED, the pipeline's default
 50 steps at guidance 7.5 with DPM-Solver++.  With --output the images form one grid (1 x len(seeds)); without it each is written to
 `<prompt with _ for spaces>_<seed>.jpg` in the working directory.
 
+--with DIR [DIR ...] composes further trained output directories with `<output_dir>` (textboost_amd/compose.py): a subject run and a style
+run trained with --mixing, "a <dog> dog in <watercolor> style".  Adapters add (`--weights W ...`, one per run including `<output_dir>`, default
+1 each; a run at weight 0 lends its tokens only), tokens are the union; a token that several runs hold keeps the first run's vector, and a
+prompt that uses such a token is refused as ambiguous.  --checkpoint N applies to `<output_dir>` only: give `.../checkpoint-N` in --with.  One
+line per run (rank, which lora_B rows it uses, weight, UNet adapters) and one on whether the adapters are disjoint are printed first.
+
 --attn-map [WORD ...] also writes where each word lands in the images (textboost_amd/attn_maps.py: the UNet's cross-attention from image
 positions to prompt tokens, averaged over heads, layers and steps of the conditional half): `<output stem>_attn.jpg`, one row of overlays per
 word and one column per seed, and `<output stem>_attn.npz` with `maps` fp32 [seeds, words, h, w], `words` and `seeds`; without --output one
-`<prompt>_<seed>_attn.jpg` / `.npz` pair per seed.  Without a word the run's placeholder tokens that occur in the prompt are taken.  The images
+`<prompt>_<seed>_attn.jpg` / `.npz` pair per seed.  Without a word the placeholder tokens (of all composed runs) that occur in the prompt are taken.  The images
 themselves do not change.
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
@@ -43,7 +50,48 @@ def build_parser():
     p.add_argument("--steps", type=int, default=50, help="sampling steps (the pipeline's default)")
     p.add_argument("--attn-map", dest="attn_map", type=str, nargs="*", default=None, metavar="WORD",
                    help="also write token attention maps of these words of the prompt (no word: the run's placeholder tokens in the prompt)")
+    p.add_argument("--with", dest="with_runs", type=str, nargs="+", default=None, metavar="DIR",
+                   help="further trained output directories composed with `path` (subject x style)")
+    p.add_argument("--weights", type=float, nargs="+", default=None, metavar="W",
+                   help="adapter weight per run, `path` first (default: 1 each)")
     return p
+
+
+def load_runs(args):
+    """`path` [--checkpoint N] and every --with directory, composed (textboost_amd/compose.py); on the host.  Without --with and --weights:
+    the one run as read."""
+    from textboost_amd import compose as C
+    from textboost_amd import generate as G
+    path = args.path.rstrip("/") or args.path
+    if args.checkpoint is not None:
+        path = os.path.join(path, f"checkpoint-{args.checkpoint}")
+    paths = [path] + [d.rstrip("/") or d for d in (args.with_runs or [])]
+    if args.weights is not None and len(args.weights) != len(paths):
+        raise SystemExit(f"inference.py: --weights: {len(args.weights)} weights for {len(paths)} runs (one per run, `path` first)")
+    runs = [G.read_run_dir(d) for d in paths]
+    if len(runs) == 1 and args.weights is None:
+        return runs[0]
+    weights = args.weights or [1.0] * len(runs)
+    for run, w in zip(runs, weights):
+        print(f"run {run.path}: rank {run.rank}, lora_B rows {C.adapter_support(run)}, weight {w:g}, UNet K/V adapters "
+              f"{'rank ' + str(run.unet_rank) if run.unet_rank else 'none'}")
+    if len(runs) > 1:
+        print("the adapters change disjoint output features of q/k/v_proj (--mixing)" if C.disjoint(runs) else
+              "the adapters are not disjoint: their deltas overlap and add")
+    try:
+        run = C.compose_runs(runs, weights)
+    except (ValueError, NotImplementedError) as e:
+        raise SystemExit(f"inference.py: --with: {e}")
+    first = {}
+    for r in runs:
+        for n, _ in r.tokens:
+            first.setdefault(n, r.path)
+    for tok, dropped in run.shadowed:
+        for what, text in [("--prompt", args.prompt)] + [("--attn-map", w) for w in (args.attn_map or [])]:
+            if tok in text:
+                raise SystemExit(f"inference.py: {what} {text!r} uses {tok}, which both {first[tok]} and {dropped} hold: ambiguous (the first "
+                                 "run's vector would be taken); rename the token in one run or leave it out of the prompt")
+    return run
 
 
 def attn_map_words(model_dir, run, prompt, requested):
@@ -99,10 +147,7 @@ def main(argv=None):
     if not args.model:
         raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
     G.check_model_dir(args.model, "inference.py")
-    path = args.path.rstrip("/") or args.path
-    if args.checkpoint is not None:
-        path = os.path.join(path, f"checkpoint-{args.checkpoint}")
-    run = G.read_run_dir(path)
+    run = load_runs(args)
     words = positions = None
     if args.attn_map is not None:        # every refusal before anything reaches the device
         words, positions = attn_map_words(args.model, run, args.prompt, args.attn_map)
@@ -115,6 +160,7 @@ def main(argv=None):
         pipe = G.Pipeline.from_model_dir(args.model, n, steps=args.steps, guidance=7.5)
         base = G.load_base_text(args.model)
         te, tokenizer = G.load_text_encoder(args.model, run, 2 * n, base=base)
+        pipe.set_run(run)
         T = base.geo.max_pos
         ids = G.tokenize(tokenizer, [""] * n + [args.prompt] * n, T).to(pipe.dev)
         states = te.forward(ids, pins=False).view(2, n * T, -1)

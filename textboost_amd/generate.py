@@ -1,9 +1,11 @@
 """Images from a trained output directory: the read side of the layout `checkpoint.py` writes, and the generation protocol of the reference's
 eval_dreambooth.py (`load_pipeline` :175-215, `generate_from_pipeline` :218-267, `generate` :270-350) and inference.py (:47-112).
 
-    read_run_dir(<path>/<instance>[/checkpoint-N]) -> TrainedRun      text_encoder/adapter_config.json + adapter_model.safetensors, <token>.bin
+    read_run_dir(<path>/<instance>[/checkpoint-N]) -> TrainedRun      text_encoder/adapter_config.json + adapter_model.safetensors, <token>.bin,
+                                                                      unet/ (the cross-attention K/V adapters of --unet_params_to_train crossattn_kv)
     load_text_encoder(model_dir, run, ...)      -> HipTextEncoder (+ tokenizer) with the adapter, the learned rows and the null-embedding pins
     Pipeline.from_model_dir(model_dir, ...)     -> UNet, VAE decoder and sampler executors, built once per run
+    Pipeline.set_unet_adapters([...])           -> attn2.to_k / to_v = W + sum w_i B_i A_i (one exact-fp32 GEMM, rounded once); [] = the base weights
     generate_instance(pipe, base, run, ...)     -> <outdir>/seed<s>/<instance>/<prompt>.png for every seed, 25 prompts each
 
 Device work: `HipTextEncoder.forward`, `HipSampler.denoise` (guided DPM-Solver++ steps on `HipUNet.forward`), `HipVAEDecoder.decode_rgbx`
@@ -18,6 +20,8 @@ Stated deviations from the reference:
     batch is padded with its last prompt and the padding image is dropped.  The reference runs 16 + 9.
   * the null embedding is the training-time one (the base encoder's output for the empty prompt, or the shipped SD2.1-base tensor); the reference
     loads `assets/start_emb_<model>.pt`, a file it does not ship.
+  * a run's `unet/` directory (the cross-attention K/V adapters of `--unet_params_to_train crossattn_kv`) is read and folded into the UNet before
+    the run is sampled; the reference's readers never open it and sample such a run with the base UNet.
   * `--model` is a local diffusers directory; UNet, decoder and sampler are built once per run and only the text encoder is reloaded per subject.
 """
 from __future__ import annotations
@@ -35,6 +39,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HUB_ALIASES = ("sd14", "sd15", "sd21base", "sd21")     # eval_dreambooth.py:18-23 / inference.py:15-20: names of hub repositories
 SKIPPED_BIN = ("optimizer.bin", "scheduler.bin")       # :199-206
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj")
+UNET_LORA_TARGETS = ("attn2.to_k", "attn2.to_v")      # checkpoint.save_unet_adapters
 MAX_PNG_THREADS = 8
 
 
@@ -128,6 +133,9 @@ class TrainedRun:
     lora: Dict[str, torch.Tensor]                       # peft adapter keys (checkpoint.lora_state_dict)
     tokens: List[Tuple[str, torch.Tensor]] = field(default_factory=list)   # (name, fp32 [D]) in loading order
     files: List[str] = field(default_factory=list)      # os.listdir(path): the identifier counts the subject's files
+    unet_rank: int = 0                                  # <path>/unet/: rank of the cross-attention K/V adapters (0: none)
+    unet_lora: Dict[str, torch.Tensor] = field(default_factory=dict)       # in-model keys (checkpoint.unet_lora_state_dict)
+    shadowed: List[Tuple[str, str]] = field(default_factory=list)          # compose.compose_runs: (token, path of the run whose vector was dropped)
 
 
 def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedRun:
@@ -177,7 +185,43 @@ def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedR
             raise ValueError(f"{model_path}/{name}: token {tok!r} has width {t.shape[1]}, the text encoder's hidden_size is {hidden_size}")
         names = [tok] + [f"{tok}_{i}" for i in range(1, t.shape[0])]    # diffusers load_textual_inversion: tok, tok_1, ..., tok_{n-1}
         tokens += [(n, t[i].clone()) for i, n in enumerate(names)]
-    return TrainedRun(path=model_path, rank=r, lora=lora, tokens=tokens, files=files)
+    unet_rank, unet_lora = read_unet_adapters(model_path)
+    return TrainedRun(path=model_path, rank=r, lora=lora, tokens=tokens, files=files, unet_rank=unet_rank, unet_lora=unet_lora)
+
+
+def read_unet_adapters(model_path: str) -> Tuple[int, Dict[str, torch.Tensor]]:
+    """<run>/unet/adapter_config.json + adapter_model.safetensors (checkpoint.save_unet_adapters) -> (rank, tensors under the in-model keys
+    `<attn2 path>.to_{k,v}.lora_{A,B}.default.weight`); (0, {}) when the run holds none.  Both key layouts of
+    `checkpoint.load_unet_peft_adapter_state_dict` are read; what the fold cannot apply is refused by name."""
+    from safetensors.torch import load_file
+    from .checkpoint import unet_adapter_in_model_keys
+    u_dir = os.path.join(model_path, "unet")
+    wpath = os.path.join(u_dir, "adapter_model.safetensors")
+    if not os.path.exists(wpath):
+        return 0, {}
+    with open(os.path.join(u_dir, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    r = int(cfg.get("r", 0))
+    if cfg.get("use_dora"):
+        raise NotImplementedError(f"{u_dir}: use_dora adapters are not built")
+    if cfg.get("use_rslora"):
+        raise NotImplementedError(f"{u_dir}: use_rslora adapters are not built (scaling alpha / sqrt(r))")
+    if r <= 0:
+        raise ValueError(f"{u_dir}: adapter_config.json has r = {r} beside an adapter_model.safetensors")
+    if cfg.get("lora_alpha", r) != r:
+        raise NotImplementedError(f"{u_dir}: lora_alpha = {cfg.get('lora_alpha')} != r = {r}: the K/V fold carries no separate LoRA scaling")
+    targets = cfg.get("target_modules") or []
+    targets = [targets] if isinstance(targets, str) else list(targets)
+    if sorted(targets) != sorted(UNET_LORA_TARGETS):
+        raise NotImplementedError(f"{u_dir}: target_modules {sorted(targets)}: only attn2.to_k / attn2.to_v adapters are built")
+    try:
+        sd = unet_adapter_in_model_keys(load_file(wpath))
+    except KeyError as e:
+        raise ValueError(f"{u_dir}: {e.args[0]}")
+    for k, v in sd.items():
+        if v.dim() != 2 or (v.shape[0] if ".lora_A." in k else v.shape[1]) != r:
+            raise ValueError(f"{u_dir}: {k} has shape {tuple(v.shape)}: not a rank-{r} adapter tensor")
+    return r, {k: v.float() for k, v in sd.items()}
 
 
 # ------------------------------------------------------------------------------------------------ text encoder of one subject
@@ -267,6 +311,10 @@ class Pipeline:
         self.unet = HipUNet(unet_geo, unet_sd, 2 * batch, size, size, text_len=text_len, device=device)
         self.vae = HipVAEDecoder(vae_geo, vae_sd, batch, size, size, device=device)
         self.sampler = HipSampler(self.unet, self.vae, steps=steps, guidance=guidance, scheduler_config=scheduler_config)
+        # the fp32 attn2.to_k / to_v weights the UNet was built from, in the layout of `HipUNet.P["kv_all.w"]`: a fold rounds them once
+        self.kv_base = torch.cat([torch.cat([unet_sd[p + ".to_k.weight"], unet_sd[p + ".to_v.weight"]], dim=0) for p, _ in self.unet.xattn],
+                                 dim=0).detach().float().to(device).contiguous()
+        self.kv_folded = False
 
     @classmethod
     def from_model_dir(cls, model_dir: str, batch: int, steps: int = 25, guidance: float = 7.5, device="cuda"):
@@ -289,6 +337,51 @@ class Pipeline:
         vsd = load_file(os.path.join(model_dir, "vae", "diffusion_pytorch_model.safetensors"))
         return cls(models.unet_geometry_from_config(ucfg), usd, vgeo, vsd, scfg, int(ucfg.get("sample_size", 64)), batch, steps, guidance,
                    text_len=text_len, device=device)
+
+    def set_unet_adapters(self, adapters: Sequence[Tuple[Dict[str, torch.Tensor], int, float]]):
+        """adapters: (state dict under the in-model keys of `TrainedRun.unet_lora`, rank, weight) per run.  Loads attn2.to_k / to_v =
+        W + sum_i w_i B_i A_i into the UNet: the products as ONE exact-fp32 GEMM `W2 A_all + W` (tb_gemm_f32_t; W2 = the block-structured
+        [w_1 B_1 | w_2 B_2 | ...], w_i B_i rounded in fp32 on the host, zero outside a projection's own columns; A_all = every down projection
+        stacked), rounded once to the executor's operand dtype by `load_kv_weight`.  No adapter (an empty list, weights 0): the base weights,
+        exactly as the UNet was built with them."""
+        from . import ops
+        unet = self.unet
+        adapters = [(sd, int(r), float(w)) for sd, r, w in adapters if int(r) > 0 and float(w) != 0.0]
+        if not adapters:
+            if self.kv_folded:
+                unet.load_kv_weight(self.kv_base)
+                self.kv_folded = False
+            return
+        Dc = self.kv_base.shape[1]
+        n = len(unet.xattn)
+        K = sum(n * 2 * r for _, r, _ in adapters)
+        w2 = torch.zeros(unet.kv_total, K, dtype=torch.float32)
+        a_all = torch.empty(K, Dc, dtype=torch.float32)
+        col = 0
+        for sd, r, w in adapters:
+            for p, C in unet.xattn:
+                ko = unet.kv_off[p]
+                for j, name in enumerate(("to_k", "to_v")):
+                    try:
+                        A, B = sd[f"{p}.{name}.lora_A.default.weight"], sd[f"{p}.{name}.lora_B.default.weight"]
+                    except KeyError as e:
+                        raise ValueError(f"UNet adapters: no tensor {e.args[0]} (the adapters belong to another UNet geometry)")
+                    if tuple(A.shape) != (r, Dc) or tuple(B.shape) != (C, r):
+                        raise ValueError(f"UNet adapters: {p}.{name} has lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)}; this UNet takes "
+                                         f"{(r, Dc)} / {(C, r)}")
+                    a_all[col:col + r] = A.float()
+                    w2[ko + j * C:ko + (j + 1) * C, col:col + r] = B.float() * w
+                    col += r
+        w2, a_all = w2.to(self.dev), a_all.to(self.dev)
+        merged = torch.empty_like(self.kv_base)
+        with ops.f32_mode(0):      # exact products whatever mode the process trains in
+            ops.gemm_f32_t(w2, a_all, merged, unet.kv_total, Dc, K, w_trans=True, R=self.kv_base)
+        unet.load_kv_weight(merged)
+        self.kv_folded = True
+
+    def set_run(self, run: "TrainedRun"):
+        """the UNet of one trained run: its K/V adapters folded in, or the base weights"""
+        self.set_unet_adapters([(run.unet_lora, run.unet_rank, 1.0)] if run.unet_rank else [])
 
     def images(self, cond, uncond, latents, what: str = "", maps=None) -> torch.Tensor:
         """text states fp32 [B*T, D] twice, latents fp32 [B, 4, size, size] on the device -> int32 RGBX [B, 8 size, 8 size] (resident).
@@ -320,6 +413,7 @@ def generate_instance(pipe: Pipeline, base: BaseText, run: TrainedRun, instance:
     if max(len(b) for b in batches) > pipe.B:
         raise ValueError(f"the executors are built for {pipe.B} prompts per batch; {max(len(b) for b in batches)} needed")
     te, tokenizer = load_text_encoder(base.model_dir, run, 2 * pipe.B, dev, base=base)
+    pipe.set_run(run)       # the run's UNet K/V adapters; the base weights again for a run without
     T = base.geo.max_pos
     # text states once per subject (they do not depend on the seed): the empty negative prompt and the batch's prompts in one encoder call
     states = []
