@@ -396,6 +396,12 @@ int tb_lora_bwd_chain(const void* dY, int64_t lddy, const void* x, int64_t ldx, 
                       void* dt, int64_t lddt, float* dA /* += */, float* dB /* += */, int64_t M, int D, int K, int r, int P,
                       float scaling, const void* pend_x, int64_t pend_ldx, const void* pend_dt, int64_t pend_lddt,
                       float* pend_dA /* += */, int da_now, tb_stream_t stream);
+/* the two weight gradients alone, for an adapter set whose dt a GEMM wrote (dt = dY @ w2_t^T, w2_t = (scaling B)^T from tb_lora_wide_pack):
+     dB[(p*D + n)*r + j] += scaling * sum_m dY[m, p*D + n] * t[m, p*r + j]        dA[(p*r + j)*K + k] += sum_m dt[m, p*r + j] * x[m, k]
+   one launch of P*D/32 + P*K/32 panels, 32 / 64 KB of LDS whatever D and K are (r <= 8; D % 32 == 0, K % 32 == 0): the out_proj / fc1 / fc2
+   adapters of --lora_target_modules, P = 1, D up to 5120.  Panel arithmetic and summation order are tb_lora_bwd's. */
+int tb_lora_bwd_panels(const void* dY, int64_t lddy, const void* x, int64_t ldx, const void* t, int64_t ldt, const void* dt, int64_t lddt,
+                       float* dA /* += */, float* dB /* += */, int64_t M, int D, int K, int r, int P, float scaling, tb_stream_t stream);
 int tb_lora_set_variant(int v);   /* profiling: 0 = the dt slabs of tb_lora_bwd load dY in loops, 1 (default) = all loads up front; returns the old value */
 /* Ranks 9 .. 64 (csrc/lora_wide.hip).  Adapter p owns columns [p*rp, p*rp + r) of t / dt: rp >= r, a multiple of 32, at most 64; Rp >= P*rp is
    the total width (the callers round it to the GEMM's K granularity); padding columns / rows are zero.  One launch packs `layers` stacked

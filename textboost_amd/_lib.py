@@ -185,6 +185,7 @@ _SIGS = {
     "tb_lora_bwd_ws_floats": ([_I64, _I, _I, _I, _I], _I64),
     "tb_lora_bwd_chain": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _I, _I, _I, _I, _F, _VP, _I64, _VP, _I64, _VP, _I,
                            _VP], C.c_int),
+    "tb_lora_bwd_panels": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _I, _I, _I, _I, _F, _VP], C.c_int),
     "tb_lora_set_variant": ([_I], C.c_int),
     "tb_lora_wide_pack": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP], C.c_int),
     "tb_lora_wide_wgrad": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _I, _I, _I, _I, _I, _F, _VP], C.c_int),

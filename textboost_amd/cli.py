@@ -83,6 +83,15 @@ FLAGS = [
 ]
 
 
+# flags the reference does not have: added by `build_parser`, NOT reported by `flag_table` (the 66-flag comparison is about the reference's CLI)
+LORA_TARGET_CHOICES = ["q_proj", "k_proj", "v_proj", "out_proj", "fc1", "fc2"]
+EXTENSION_FLAGS = [
+    # which Linear layers of every CLIP layer carry a rank --lora_rank adapter; the wider list is the one the reference keeps as a comment beside
+    # its target_modules line (train_textboost.py:706)
+    ("--lora_target_modules", dict(type="str", nargs="+", default=["q_proj", "k_proj", "v_proj"], choices=LORA_TARGET_CHOICES, metavar="M")),
+]
+
+
 def flag_table():
     """Normalised view used by the parity test (same schema as tests/golden/cli_flags.json)."""
     out = []
@@ -95,7 +104,7 @@ def flag_table():
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="TextBoost training on MI355X (HIP kernels behind the reference CLI).")
-    for name, kw in FLAGS:
+    for name, kw in FLAGS + EXTENSION_FLAGS:
         kw = dict(kw)
         if "type" in kw:
             kw["type"] = _T[kw["type"]]
@@ -118,4 +127,8 @@ def parse_args(input_args=None):
             warnings.warn("You need not use --class_token without --with_image_prior.")
     if args.augment_inversion and not bool(args.augment_prompt):
         raise ValueError("You need to use --augment_prompt=1 with --augment_prompt.")
+    missing = [m for m in ("q_proj", "k_proj", "v_proj") if m not in args.lora_target_modules]
+    if missing:  # q/k/v are one three-adapter kernel set, and the reference always trains them
+        raise ValueError(f"--lora_target_modules must contain q_proj k_proj v_proj; {' '.join(missing)} missing")
+    args.lora_target_modules = [m for m in LORA_TARGET_CHOICES if m in args.lora_target_modules]   # canonical order, duplicates dropped
     return args

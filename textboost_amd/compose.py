@@ -8,6 +8,9 @@ Host only: no kernel library, no device.  Composition is rank concatenation.  Wi
 B_c = [w_1 B_1 | w_2 B_2 | ...] side by side, B_c A_c = sum_i w_i B_i A_i, so the result is ONE adapter of rank sum r_i with lora_alpha = r
 (scaling 1) and the adapter kernels apply it as they apply any other; the only arithmetic is w_i * B_i, in fp32.  The UNet cross-attention K/V
 adapters (`TrainedRun.unet_lora`) compose by the same identity.
+
+Runs may adapt different modules beyond q/k/v (--lora_target_modules: out_proj / fc1 / fc2).  A module takes the ranks of the runs that adapt it;
+the encoder runs ONE rank, so every module is padded to the common rank sum r_i with zero rows of A and zero columns of B, which add exact zeros.
 """
 from __future__ import annotations
 
@@ -16,18 +19,23 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .generate import LORA_TARGETS, MAX_LORA_RANK, TrainedRun
+from .generate import LORA_EXTRA_TARGETS, LORA_TARGETS, MAX_LORA_RANK, TrainedRun
 
-_KEY = re.compile(r"^(?P<module>.*\.layers\.(?P<layer>\d+)\.self_attn\.(?P<proj>[a-z]_proj))\.lora_(?P<which>[AB])\.weight$")
+_KEY = re.compile(r"^(?P<module>.*\.layers\.(?P<layer>\d+)\.(?:self_attn\.(?P<proj>[a-z]+_proj)|mlp\.(?P<fc>fc[12])))\.lora_(?P<which>[AB])\.weight$")
+
+
+def _proj(m) -> str:
+    return m.group("proj") or m.group("fc")
 
 
 def _modules(run: TrainedRun) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
-    """module name (`...layers.{i}.self_attn.{q,k,v}_proj`) -> (lora_A [r, D], lora_B [D, r]); a key of any other form is refused"""
+    """module name (`...layers.{i}.self_attn.{q,k,v,out}_proj`, `...layers.{i}.mlp.fc{1,2}`) -> (lora_A [r, K], lora_B [N, r]); a key of any
+    other form is refused"""
     halves: Dict[str, Dict[str, torch.Tensor]] = {}
     for k, v in run.lora.items():
         m = _KEY.match(k)
-        if not m or m.group("proj") not in LORA_TARGETS:
-            raise ValueError(f"{run.path}: {k!r} is not a q_proj / k_proj / v_proj adapter key")
+        if not m or _proj(m) not in LORA_TARGETS + LORA_EXTRA_TARGETS:
+            raise ValueError(f"{run.path}: {k!r} is not a q_proj / k_proj / v_proj / out_proj / fc1 / fc2 adapter key")
         halves.setdefault(m.group("module"), {})[m.group("which")] = v
     out = {}
     for name, h in halves.items():
@@ -39,7 +47,8 @@ def _modules(run: TrainedRun) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
 
 def _geometry(run: TrainedRun, modules) -> Tuple[int, int]:
     """(hidden size, layer count) of a run's adapter"""
-    widths = {int(a.shape[1]) for a, _ in modules.values()} | {int(b.shape[0]) for _, b in modules.values()}
+    square = [ab for n, ab in modules.items() if n.endswith("_proj")]       # (fc1 / fc2 are hidden x intermediate)
+    widths = {int(a.shape[1]) for a, _ in square} | {int(b.shape[0]) for _, b in square}
     if len(widths) != 1:
         raise ValueError(f"{run.path}: the adapter tensors disagree in width: {sorted(widths)}")
     return widths.pop(), 1 + max(int(_KEY.match(n + ".lora_A.weight").group("layer")) for n in modules)
@@ -101,17 +110,33 @@ def compose_runs(runs: Sequence[TrainedRun], weights: Optional[Sequence[float]] 
             raise ValueError(f"compose_runs: hidden size {geo[0]} of {run.path} != {first_geo[0]} of {first[0].path}")
         if geo[1] != first_geo[1]:
             raise ValueError(f"compose_runs: {geo[1]} layers in {run.path} != {first_geo[1]} in {first[0].path}")
-        if set(mods) != set(first[1]):
-            odd_one = sorted(set(mods) ^ set(first[1]))[0]
+        # q/k/v: every run, every layer.  out_proj / fc1 / fc2: a run adapts one in every layer or in none (the encoder has no per-layer choice)
+        qkv = lambda ms: {n for n in ms if n.rsplit(".", 1)[1] in LORA_TARGETS}   # noqa: E731
+        if qkv(mods) != qkv(first[1]):
+            odd_one = sorted(qkv(mods) ^ qkv(first[1]))[0]
             raise ValueError(f"compose_runs: {run.path} and {first[0].path} adapt different modules (e.g. {odd_one})")
+    for run, mods, _ in used:
+        for x in LORA_EXTRA_TARGETS:
+            have = [n for n in mods if n.rsplit(".", 1)[1] == x]
+            if have and len(have) != first_geo[1]:
+                raise ValueError(f"compose_runs: {run.path} adapts {x} in {len(have)} of {first_geo[1]} layers (different modules per layer)")
     ranks = [run.rank for run, _, _ in used]
     if sum(ranks) > MAX_LORA_RANK:
         raise NotImplementedError(f"compose_runs: ranks {' + '.join(map(str, ranks))} = {sum(ranks)}: the text-encoder adapter kernels take "
                                   f"r <= {MAX_LORA_RANK}")
     lora: Dict[str, torch.Tensor] = {}
     if used:
-        for name in used[0][1]:
-            A, B = _concat([(mods[name][0], mods[name][1], w) for _, mods, w in used])
+        names = list(used[0][1]) + sorted({n for _, mods, _ in used[1:] for n in mods} - set(used[0][1]))
+        for name in names:
+            parts = [(mods[name][0], mods[name][1], w) for _, mods, w in used if name in mods]
+            shapes = {(int(a.shape[1]), int(b.shape[0])) for a, b, _ in parts}
+            if len(shapes) != 1:
+                raise ValueError(f"compose_runs: the runs disagree in the shape of {name}: {sorted(shapes)}")
+            A, B = _concat(parts)
+            if A.shape[0] < sum(ranks):   # a module only some runs adapt: zero A rows / zero B columns up to the rank every module runs at
+                pad = sum(ranks) - A.shape[0]
+                A = torch.cat([A.float(), torch.zeros(pad, A.shape[1])], dim=0).contiguous()
+                B = torch.cat([B.float(), torch.zeros(B.shape[0], pad)], dim=1).contiguous()
             lora[name + ".lora_A.weight"], lora[name + ".lora_B.weight"] = A, B
     # ---- tokens
     width = first_geo[0] if first_geo else None

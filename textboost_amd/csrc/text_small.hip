@@ -489,6 +489,33 @@ extern "C" int tb_lora_bwd_chain(const void* dY, int64_t lddy, const void* x, in
   return TB_OK;
 }
 
+// Both weight gradients of an adapter set whose dt a GEMM already wrote (dt = dY @ (scaling B)^T on the packed w2_t operand): the P*D/32 dB panels
+// and the P*K/32 dA panels in ONE launch, no dt slabs -- so no copy of B in LDS (the slab form stages all of B per 16 rows: 96 KB at D = 3072,
+// r = 8) and nothing that grows with D but the panel count.  The rectangular MLP adapters (fc1: D = 3072 / 5120, fc2: K = 3072 / 5120) run here.
+// Panel arithmetic and summation order are tb_lora_bwd's.
+extern "C" int tb_lora_bwd_panels(const void* dY, int64_t lddy, const void* x, int64_t ldx, const void* t, int64_t ldt, const void* dt,
+                                  int64_t lddt, float* dA, float* dB, int64_t M, int D, int K, int r, int P, float scaling,
+                                  tb_stream_t stream) {
+  (void)hipGetLastError();  // drop any stale (non-sticky) error left by an earlier runtime call
+  if (!dY || !x || !t || !dt || !dA || !dB || r <= 0 || r > 8 || P <= 0 || P * r > LORA_MAXR || M <= 0 || D <= 0 || K <= 0) return TB_EINVAL;
+  if (D % LORA_PANEL || K % LORA_PANEL || lddy % 8 || ldx % 8) return TB_EINVAL;  // 16-byte vector accesses, panels inside one adapter
+  if (((uintptr_t)dY) % 16 || ((uintptr_t)x) % 16) return TB_EINVAL;
+  if (lddy < (int64_t)P * D || ldx < K || ldt < (int64_t)P * r || lddt < (int64_t)P * r) return TB_EINVAL;
+  const int RR = r <= 4 ? 4 : 8;
+  if (r == RR && (((uintptr_t)t) % (2 * RR) || ((uintptr_t)dt) % (2 * RR))) return TB_EINVAL;   // (the panels read a row's r values as one vector)
+  const size_t red_bytes = (size_t)LORA_SLOTS * LORA_PANEL * RR * sizeof(float);
+  const int grid = P * (D / LORA_PANEL) + P * (K / LORA_PANEL);
+  hipStream_t s = (hipStream_t)stream;
+  if (RR == 4)
+    hipLaunchKernelGGL((lora_bwd_dt_db_kernel<4, 0>), dim3(grid), dim3(256), red_bytes, s, (const f16*)dY, lddy, (const f16*)t, ldt,
+                       (const float*)nullptr, (f16*)nullptr, (int64_t)0, dB, M, D, r, P, scaling, 0, (const f16*)x, ldx, (const f16*)dt, lddt, dA, K);
+  else
+    hipLaunchKernelGGL((lora_bwd_dt_db_kernel<8, 0>), dim3(grid), dim3(256), red_bytes, s, (const f16*)dY, lddy, (const f16*)t, ldt,
+                       (const float*)nullptr, (f16*)nullptr, (int64_t)0, dB, M, D, r, P, scaling, 0, (const f16*)x, ldx, (const f16*)dt, lddt, dA, K);
+  TB_CHECK_LAUNCH();
+  return TB_OK;
+}
+
 extern "C" int tb_lora_bwd(const void* dY, int64_t lddy, const void* x, int64_t ldx, const void* t, int64_t ldt, const float* Bcat,
                            void* dt, int64_t lddt, float* dA, float* dB, float* ws, int64_t M, int D, int K, int r, int P,
                            float scaling, tb_stream_t stream) {

@@ -39,6 +39,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HUB_ALIASES = ("sd14", "sd15", "sd21base", "sd21")     # eval_dreambooth.py:18-23 / inference.py:15-20: names of hub repositories
 SKIPPED_BIN = ("optimizer.bin", "scheduler.bin")       # :199-206
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj")
+LORA_EXTRA_TARGETS = ("out_proj", "fc1", "fc2")     # --lora_target_modules may add these (text_encoder.LORA_EXTRA)
+
+
+def lora_targets_of(lora) -> Tuple[str, ...]:
+    """the adapted modules of a peft adapter state dict (`...{self_attn,mlp}.<module>.lora_{A,B}.weight`), q/k/v first"""
+    held = {k.split(".")[-3] for k in lora}
+    return tuple(n for n in LORA_TARGETS + LORA_EXTRA_TARGETS if n in held)
 UNET_LORA_TARGETS = ("attn2.to_k", "attn2.to_v")      # checkpoint.save_unet_adapters
 MAX_PNG_THREADS = 8
 
@@ -159,14 +166,18 @@ def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedR
         raise NotImplementedError(f"{te_dir}: rank-{r} adapters are not built (the text-encoder adapter kernels take r <= {MAX_LORA_RANK})")
     targets = cfg.get("target_modules") or []
     targets = [targets] if isinstance(targets, str) else list(targets)
-    if r and sorted(targets) != sorted(LORA_TARGETS):
-        raise NotImplementedError(f"{te_dir}: target_modules {sorted(targets)}: only q_proj / k_proj / v_proj adapters are built")
+    if r and (set(targets) - set(LORA_TARGETS + LORA_EXTRA_TARGETS) or not set(LORA_TARGETS) <= set(targets)):
+        raise NotImplementedError(f"{te_dir}: target_modules {sorted(targets)}: adapters are built for q_proj / k_proj / v_proj (always all three) "
+                                  "and, beside them, out_proj / fc1 / fc2")
     lora = load_file(os.path.join(te_dir, "adapter_model.safetensors")) if r else {}
     if r:
+        held = {k.split(".")[-3] for k in lora}
+        if held != set(targets):   # (a listed module without tensors would silently run un-adapted; tensors of an unlisted one would be dropped)
+            raise NotImplementedError(f"{te_dir}: target_modules {sorted(targets)}, but adapter_model.safetensors holds tensors of {sorted(held)}")
         a = [v for k, v in lora.items() if k.endswith("lora_A.weight")]
         if not a or any(t.shape[0] != r for t in a):
             raise ValueError(f"{te_dir}: adapter_model.safetensors does not hold rank-{r} lora_A tensors")
-        hidden_size = hidden_size or int(a[0].shape[1])
+        hidden_size = hidden_size or int(next(v for k, v in lora.items() if k.endswith("q_proj.lora_A.weight")).shape[1])
     files = sorted(os.listdir(model_path))
     tokens: List[Tuple[str, torch.Tensor]] = []
     for name in files:
@@ -272,7 +283,8 @@ def load_text_encoder(model_dir: str, run: TrainedRun, batch: int, device="cuda"
         raise FileNotFoundError(f"{tdir}: no vocab.json (only local tokenizer files can be loaded)")
     from transformers import CLIPTokenizer
     tokenizer = CLIPTokenizer.from_pretrained(tdir, local_files_only=True)     # (train_textboost.load_tokenizer)
-    te = HipTextEncoder(geo, base.state_dict, batch, mode="autocast", lora_rank=run.rank, device=device)
+    te = HipTextEncoder(geo, base.state_dict, batch, mode="autocast", lora_rank=run.rank, device=device,
+                        lora_targets=lora_targets_of(run.lora) if run.rank else None)
     if run.rank:
         ckpt.load_lora_state_dict(te, run.lora)
         te.pack_lora()

@@ -809,6 +809,36 @@ def lora_wide_wgrad(dY, x, t, dt, dA, dB, D, K, r, rp, P, scaling=1.0):
                                        L.ptr(dB), M, D, K, r, rp, P, scaling, L.stream()), "tb_lora_wide_wgrad")
 
 
+def lora_rect_dims(r):
+    """(rp, Rp) of ONE adapter on a 64-column K-extension (out_proj / fc1 / fc2: P = 1): its columns are [0, r) at every rank, so that one pack
+    launch (tb_lora_wide_pack, rp a multiple of 32) serves the VALU kernels (r <= 8) and the MFMA ones alike"""
+    assert 0 < r <= LORA_MAX_RANK, r
+    return (r + 31) // 32 * 32, 64
+
+
+def lora_bwd_panels(dY, x, t, dt, dA, dB, D, K, r, P=1, scaling=1.0):
+    """tb_lora_bwd_panels (r <= 8): dB += scaling * dY_p^T t_p and dA += dt_p^T x in one launch, for a dt that a GEMM wrote (16-bit operands)."""
+    M = x.shape[0]
+    assert dY.shape[0] == M and t.shape[0] == M and dt.shape[0] == M and dY.shape[1] == P * D and x.shape[1] == K
+    assert dA.is_contiguous() and dB.is_contiguous() and dA.numel() == P * r * K and dB.numel() == P * D * r
+    assert dA.dtype == torch.float32 and dB.dtype == torch.float32
+    for o in (dY, x, t, dt):
+        assert _dt(o) == L.TB_F16 and o.stride(1) == 1
+    L.check(L.lib().tb_lora_bwd_panels(L.ptr(dY), dY.stride(0), L.ptr(x), x.stride(0), L.ptr(t), t.stride(0), L.ptr(dt), dt.stride(0), L.ptr(dA),
+                                       L.ptr(dB), M, D, K, r, P, scaling, L.stream()), "tb_lora_bwd_panels")
+
+
+def lora_rect_bwd(dY, x, t, w2_t, dt, dA, dB, D, K, r, scaling=1.0):
+    """the backward of one rectangular adapter (y += scaling * (x A^T) B^T, A [r, K], B [D, r]) in the 16-bit modes: dt [M, 64] = dY @ w2_t^T as a
+    GEMM (columns >= r come out zero: w2_t's padding rows), then both weight gradients in one launch -- VALU panels up to rank 8, the MFMA tiles
+    of csrc/lora_wide.hip above.  Nothing here stages B in LDS, so the cost does not depend on D beyond the products themselves."""
+    gemm(dY, w2_t, dt)
+    if r <= LORA_NARROW_MAX:
+        lora_bwd_panels(dY, x, t, dt, dA, dB, D, K, r, 1, scaling)
+    else:
+        lora_wide_wgrad(dY, x, t, dt, dA, dB, D, K, r, lora_rect_dims(r)[0], 1, scaling)
+
+
 _lora_ws = {}
 
 

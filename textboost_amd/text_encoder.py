@@ -11,6 +11,9 @@ Three numeric modes, matching how the reference runs the two encoders (SURVEY.md
   * "fp32"     -- no mixed precision (the default, :298-308; weight_dtype stays float32, :930-939): every parameter, activation
     and gradient fp32, for the trainable encoder and the teacher alike (csrc/f32_path.hip).
 
+`lora_targets` (--lora_target_modules) may add out_proj / fc1 / fc2 to q/k/v: one adapter each (P = 1) on a 64-column K-extension of its own,
+masters in `extra[name].A [L, r, K_in]` / `.B [L, D_out, r]`.
+
 All arithmetic is in libtextboost_hip.so; this file owns parameters, buffers and the layer schedule.
 Trainable state lives in three flat fp32 buffers so the optimizer / all-reduce see one tensor each:
   lora_A [L, 3r, D], lora_B [L, 3D, r]  and the token table [V + k, D] (rows >= first_added train).
@@ -19,7 +22,8 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from types import SimpleNamespace
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -42,13 +46,34 @@ class CLIPGeometry:
     eps: float = 1e-5
 
 
+LORA_QKV = ("q_proj", "k_proj", "v_proj")
+LORA_EXTRA = ("out_proj", "fc1", "fc2")      # in the order their masters lie in the trainer's flat buffers
+_EXTRA_W = {"out_proj": "out", "fc1": "fc1", "fc2": "fc2"}
+
+
+def check_lora_targets(targets: Optional[Sequence[str]]):
+    """-> the extra modules (a sub-tuple of LORA_EXTRA) of a --lora_target_modules list; q/k/v are one P = 3 kernel set and always adapted"""
+    if targets is None:
+        return ()
+    targets = list(targets)
+    bad = [t for t in targets if t not in LORA_QKV + LORA_EXTRA]
+    if bad:
+        raise ValueError(f"--lora_target_modules: unknown module {bad[0]!r} (choices: {' '.join(LORA_QKV + LORA_EXTRA)})")
+    missing = [t for t in LORA_QKV if t not in targets]
+    if missing:
+        raise ValueError(f"--lora_target_modules must contain q_proj k_proj v_proj (one kernel set; the reference always trains them): "
+                         f"{' '.join(missing)} missing")
+    return tuple(n for n in LORA_EXTRA if n in targets)
+
+
 HF_LAYER = {"ln1": "layer_norm1", "ln2": "layer_norm2", "q": "self_attn.q_proj", "k": "self_attn.k_proj", "v": "self_attn.v_proj",
             "out": "self_attn.out_proj", "fc1": "mlp.fc1", "fc2": "mlp.fc2"}
 
 
 class HipTextEncoder:
     def __init__(self, geo: CLIPGeometry, state_dict: Dict[str, torch.Tensor], batch: int, mode: str = "autocast", lora_rank: int = 0,
-                 lora_alpha: Optional[float] = None, n_slots: int = 1, device="cuda", seed: Optional[int] = None):
+                 lora_alpha: Optional[float] = None, n_slots: int = 1, device="cuda", seed: Optional[int] = None,
+                 lora_targets: Optional[Sequence[str]] = None):
         """state_dict uses transformers CLIPTextModel keys (`text_model.embeddings.token_embedding.weight`, ...)."""
         assert mode in ("autocast", "half", "fp32")
         assert geo.act in ("quick_gelu", "gelu")  # SD1.x CLIP-L / SD2.x OpenCLIP-H
@@ -95,6 +120,8 @@ class HipTextEncoder:
         self.first_added = self.token_table.shape[0]
         self.n_added = 0
         self.wide = False
+        self.extra: Dict[str, SimpleNamespace] = {}
+        self.lora_targets = LORA_QKV + check_lora_targets(lora_targets)
         if self.r > ops.LORA_MAX_RANK:
             raise NotImplementedError(f"text-encoder LoRA rank {self.r}: ranks up to {ops.LORA_MAX_RANK} are supported")
         if self.r:
@@ -116,6 +143,20 @@ class HipTextEncoder:
                 self.a_pad = torch.zeros(Lr, self.lw, D, device=device, dtype=odt)
                 # weight of the dt GEMM; the fp32 mode multiplies by w2_fwd through a transposed view instead
                 self.w2_t = None if mode == "fp32" else torch.zeros(Lr, self.lw, 3 * D, device=device, dtype=odt)
+            # out_proj / fc1 / fc2 (drawn after q/k/v from the same generator: the default list draws what it always drew)
+            I = geo.intermediate_size
+            for name in self.lora_targets[3:]:
+                Kin, Dout = {"out_proj": (D, D), "fc1": (D, I), "fc2": (I, D)}[name]
+                X = SimpleNamespace(K=Kin, D=Dout, w=_EXTRA_W[name])
+                X.A = (torch.randn(Lr, self.r, Kin, generator=g) / self.r).to(device)
+                X.B = torch.zeros(Lr, Dout, self.r, device=device)
+                X.grad_A, X.grad_B = torch.zeros_like(X.A), torch.zeros_like(X.B)
+                X.rp = ops.lora_rect_dims(self.r)[0]
+                X.a_pad = torch.zeros(Lr, 64, Kin, device=device, dtype=odt)
+                X.w2_fwd = torch.zeros(Lr, Dout, 64, device=device, dtype=odt)
+                X.w2_dgrad = torch.zeros(Lr, Kin, 64, device=device, dtype=odt)
+                X.w2_t = None if mode == "fp32" else torch.zeros(Lr, 64, Dout, device=device, dtype=odt)   # weight of the dt GEMM
+                self.extra[name] = X
 
     # ------------------------------------------------------------------ reference-facing surface
     def set_null_embedding(self, null):  # text_encoder.py:28-32
@@ -160,6 +201,8 @@ class HipTextEncoder:
             return
         D = self.geo.hidden_size
         assert self.lora_A.is_contiguous() and self.lora_B.is_contiguous()
+        for X in self.extra.values():   # one launch per extra module: every operand of its two-source GEMMs, of its down projection and of its dt GEMM
+            ops.lora_wide_pack(X.A, X.B, X.a_pad, X.w2_fwd, X.w2_t, X.w2_dgrad, X.D, X.K, self.r, X.rp, 1, self.scaling, layers=self.geo.num_layers)
         if self.wide:
             ops.lora_wide_pack(self.lora_A, self.lora_B, self.a_pad, self.w2_fwd, self.w2_t, self.w2_dgrad, D, D, self.r, self.rp, 3, self.scaling,
                                layers=self.geo.num_layers)
@@ -184,6 +227,18 @@ class HipTextEncoder:
         ids = input_ids.reshape(-1).contiguous()
         s = f"s{slot}."
         self._bufs[s + "ids"] = ids
+        xl = self.extra
+        gemm_down = self.wide or full32   # the down projection as a GEMM on a_pad; else tb_lora_down / the LayerNorm launch, on the fp32 masters
+
+        def down(name, xin, p, i):
+            """t [M, 64] of an extra adapter: rows < Ms = xin @ A^T in columns [0, r); padding columns and the frozen extra rows stay zero"""
+            t_ = self.buf(p + "t_" + name, M, 64, f16)
+            if gemm_down:
+                ops.gemm(xin[:Ms], xl[name].a_pad[i], t_[:Ms])
+            else:
+                ops.lora_down(xin[:Ms], xl[name].A[i], t_[:Ms])
+            return t_
+
         h = self.buf(s + "h0", M, D, rdt)
         ops.embed_fwd(ids, self.token_table, self.pos_table, h[:Ms], T)
         if extra_ids is not None:
@@ -212,15 +267,31 @@ class HipTextEncoder:
             lse = self.buf(p + "lse", B * H, T, f32)
             ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], o, lse, B, H, T, T, hd, causal=True)
             h2 = self.buf(p + "h2", M, D, rdt)
-            ops.gemm(o, W["out.w"], h2, bias=W["out.b"], R=h)
-            x2 = self.buf(s + "x2", M, D, f16)
+            if "out_proj" in xl:
+                ops.gemm(o, W["out.w"], h2, A2=down("out_proj", o, p, i), W2=xl["out_proj"].w2_fwd[i], bias=W["out.b"], R=h)
+            else:
+                ops.gemm(o, W["out.w"], h2, bias=W["out.b"], R=h)
+            # (an adapted fc1 / fc2 needs its input again in the backward, for dA = dt^T x: that layer input is then kept per layer)
+            x2 = self.buf((p if "fc1" in xl else s) + "x2", M, D, f16)
             ls2 = self.buf(p + "ls2", M, 2, f32)
-            ops.layernorm_fwd(h2, x2, W["ln2.g"], W["ln2.b"], ls2, geo.eps)
-            a = self.buf(s + "a", M, I, f16)
+            a = self.buf((p if "fc2" in xl else s) + "a", M, I, f16)
             pre = self.buf(p + "pre", M, I, f16)
-            ops.gemm(x2, W["fc1.w"], a, bias=W["fc1.b"], act=self.act_fwd, C2=pre)
+            if "fc1" in xl:
+                if gemm_down:
+                    ops.layernorm_fwd(h2, x2, W["ln2.g"], W["ln2.b"], ls2, geo.eps)
+                    t1 = down("fc1", x2, p, i)
+                else:   # the down projection rides in the LayerNorm launch, as q/k/v's does in LayerNorm 1
+                    t1 = self.buf(p + "t_fc1", M, 64, f16)
+                    ops.layernorm_fwd(h2, x2, W["ln2.g"], W["ln2.b"], ls2, geo.eps, lora_A=xl["fc1"].A[i], t=t1, lora_rows=Ms)
+                ops.gemm(x2, W["fc1.w"], a, A2=t1, W2=xl["fc1"].w2_fwd[i], bias=W["fc1.b"], act=self.act_fwd, C2=pre)
+            else:
+                ops.layernorm_fwd(h2, x2, W["ln2.g"], W["ln2.b"], ls2, geo.eps)
+                ops.gemm(x2, W["fc1.w"], a, bias=W["fc1.b"], act=self.act_fwd, C2=pre)
             h3 = self.buf(p + "h3", M, D, rdt)
-            ops.gemm(a, W["fc2.w"], h3, bias=W["fc2.b"], R=h2)
+            if "fc2" in xl:
+                ops.gemm(a, W["fc2.w"], h3, A2=down("fc2", a, p, i), W2=xl["fc2"].w2_fwd[i], bias=W["fc2.b"], R=h2)
+            else:
+                ops.gemm(a, W["fc2.w"], h3, bias=W["fc2.b"], R=h2)
             h = h3
         out = self.buf(s + "out", M, D, rdt)
         lsf = self.buf(s + "lsf", M, 2, f32)
@@ -236,17 +307,23 @@ class HipTextEncoder:
         if self.r:
             self.grad_A.zero_()
             self.grad_B.zero_()
+            for X in self.extra.values():
+                X.grad_A.zero_()
+                X.grad_B.zero_()
         if self.n_added:
             self.grad_added.zero_()
 
     def backward(self, d_out, slot=0, pins=True, grads=None):
         """d_out: fp32 [B*T, D] gradient of the (scaled) loss w.r.t. forward(slot)'s output. Accumulates into
-        grad_A / grad_B / grad_added -- or into `grads` = (grad_A, grad_B, grad_added) when given: two backward passes that run
+        grad_A / grad_B / grad_added -- or into `grads` = (grad_A, grad_B, grad_added[, {extra module: (grad_A, grad_B)}]) when given: two backward passes that run
         CONCURRENTLY on two streams (the trainer's instance-prompt and prior-prompt chains) must not add into the same buffers.
         All scratch is keyed by `slot` for the same reason."""
         assert self.mode in ("autocast", "fp32")
-        grad_A, grad_B, grad_added = grads if grads is not None else (self.grad_A if self.r else None, self.grad_B if self.r else None,
-                                                                      self.grad_added if self.n_added else None)
+        grad_A, grad_B, grad_added = grads[:3] if grads is not None else (self.grad_A if self.r else None, self.grad_B if self.r else None,
+                                                                          self.grad_added if self.n_added else None)
+        xl = self.extra
+        assert grads is None or not xl or len(grads) == 4, "an encoder with extra adapted modules needs their gradient buffers too"
+        grad_x = grads[3] if grads is not None and xl else {n: (X.grad_A, X.grad_B) for n, X in xl.items()}
         full32 = self.mode == "fp32"
         geo, T = self.geo, self.T
         D, I, H = geo.hidden_size, geo.intermediate_size, geo.num_heads
@@ -257,6 +334,19 @@ class HipTextEncoder:
         B = M // T
         f16, f32 = self.op_dtype, torch.float32
         gs = f"g{slot}."
+
+        def extra_bwd(name, i, dY, x):
+            """dt of extra adapter `name` of layer i (the second K source of that Linear's dgrad GEMM); its dA / dB are added on the way"""
+            X = xl[name]
+            t_ = self._bufs[f"{s}l{i}.t_{name}"][:M]
+            dt_ = self.buf(gs + "dt_" + name, M, 64, f16)
+            gA, gB = grad_x[name]
+            if full32:
+                ops.lora_bwd(dY, x, t_, X.B[i], dt_, gA[i], gB[i], X.D, X.K, self.r, 1, self.scaling, w2_fwd=X.w2_fwd[i])
+            else:
+                ops.lora_rect_bwd(dY, x, t_, X.w2_t[i], dt_, gA[i], gB[i], X.D, X.K, self.r, self.scaling)
+            return dt_
+
         if pins:
             ops.pin_bwd(d_out, ids, B, T, self.use_fixed_special_embedding, EOS_ID)
         h_last = self._bufs[f"{s}l{geo.num_layers - 1}.h3"][:M]
@@ -275,13 +365,24 @@ class HipTextEncoder:
             lse = self._bufs[p + "lse"][:B * H]
             x1 = self._bufs[p + "x1"][:M]
             dpre = self.buf(gs + "dpre", M, I, f16)
-            ops.gemm(dh if full32 else dh16, W["fc2.wd"], dpre, act=self.act_bwd, C2=pre)
+            dy = dh if full32 else dh16
+            if "fc2" in xl:
+                ops.gemm(dy, W["fc2.wd"], dpre, A2=extra_bwd("fc2", i, dy, self._bufs[p + "a"][:M]), W2=xl["fc2"].w2_dgrad[i], act=self.act_bwd, C2=pre)
+            else:
+                ops.gemm(dy, W["fc2.wd"], dpre, act=self.act_bwd, C2=pre)
             dx2 = self.buf(gs + "dx", M, D, f16)
-            ops.gemm(dpre, W["fc1.wd"], dx2)
+            if "fc1" in xl:
+                ops.gemm(dpre, W["fc1.wd"], dx2, A2=extra_bwd("fc1", i, dpre, self._bufs[p + "x2"][:M]), W2=xl["fc1"].w2_dgrad[i])
+            else:
+                ops.gemm(dpre, W["fc1.wd"], dx2)
             dh2 = dh_other
             ops.layernorm_bwd(dx2, h2, W["ln2.g"], self._bufs[p + "ls2"], dh2, add=dh, dx16=dh16)
             do = self.buf(gs + "do", M, D, f16)
-            ops.gemm(dh2 if full32 else dh16, W["out.wd"], do)
+            dy = dh2 if full32 else dh16
+            if "out_proj" in xl:
+                ops.gemm(dy, W["out.wd"], do, A2=extra_bwd("out_proj", i, dy, o), W2=xl["out_proj"].w2_dgrad[i])
+            else:
+                ops.gemm(dy, W["out.wd"], do)
             dqkv = self.buf(gs + "dqkv", M, 3 * D, f16)
             delta = self.buf(gs + "delta", B * H, T, f32)
             ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], o, lse, do, delta, dqkv[:, :D], dqkv[:, D:2 * D],

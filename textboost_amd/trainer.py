@@ -144,15 +144,27 @@ class TextBoostStep:
         nUA = unet.kv_lora_A.numel() if getattr(unet, "kv_r", 0) else 0
         nUB = unet.kv_lora_B.numel() if nUA else 0
         self.n_unet = nUA + nUB
-        self.flat_grad = torch.zeros(nA + nB + nE + self.n_unet, device=device)
+        # --lora_target_modules: the out_proj / fc1 / fc2 masters lie behind the q/k/v ones, [A_qkv | B_qkv | A_x B_x per extra module | added rows |
+        # UNet adapters] -- the same optimizer group, clip group, learning rate and decay (peft hands them out as one parameter list, :828-841);
+        # with the default list nothing moves
+        extra = list(te.extra.values()) if has_lora else []
+        nX = sum(X.A.numel() + X.B.numel() for X in extra)
+        self.flat_grad = torch.zeros(nA + nB + nX + nE + self.n_unet, device=device)
         if has_lora:
-            self.flat_lora = torch.cat([te.lora_A.reshape(-1), te.lora_B.reshape(-1)])  # fp32 masters, flat
+            self.flat_lora = torch.cat([te.lora_A.reshape(-1), te.lora_B.reshape(-1)] + [t.reshape(-1) for X in extra for t in (X.A, X.B)])  # fp32 masters, flat
             te.lora_A = self.flat_lora[:nA].view_as(te.lora_A)
-            te.lora_B = self.flat_lora[nA:].view_as(te.lora_B)
+            te.lora_B = self.flat_lora[nA:nA + nB].view_as(te.lora_B)
             te.grad_A = self.flat_grad[:nA].view_as(te.lora_A)
             te.grad_B = self.flat_grad[nA:nA + nB].view_as(te.lora_B)
+            o = nA + nB
+            for X in extra:
+                a, b = X.A.numel(), X.B.numel()
+                X.A, X.grad_A = self.flat_lora[o:o + a].view_as(X.A), self.flat_grad[o:o + a].view_as(X.A)
+                X.B, X.grad_B = self.flat_lora[o + a:o + a + b].view_as(X.B), self.flat_grad[o + a:o + a + b].view_as(X.B)
+                o += a + b
         else:
             self.flat_lora = torch.zeros(0, device=device)
+        nBq, nB = nB, nB + nX   # (below, "nA + nB" is the end of the encoder's adapter block)
         te.grad_added = self.flat_grad[nA + nB:nA + nB + nE].view(te.n_added, D)
         self.n_lora = nA + nB
         self.n_emb = nE
@@ -240,8 +252,15 @@ class TextBoostStep:
             self.side2 = torch.cuda.Stream(device=device, priority=prio)
             self.side = torch.cuda.Stream(device=device, priority=prio)
             self.flat_grad_p = torch.zeros(nA + nB + nE, device=device)
-            self.grads_p = ((self.flat_grad_p[:nA].view_as(te.lora_A), self.flat_grad_p[nA:nA + nB].view_as(te.lora_B)) if has_lora else (None, None)) \
+            self.grads_p = ((self.flat_grad_p[:nA].view_as(te.lora_A), self.flat_grad_p[nA:nA + nBq].view_as(te.lora_B)) if has_lora else (None, None)) \
                 + (self.flat_grad_p[nA + nB:].view(te.n_added, D),)
+            if extra:
+                o, gx = nA + nBq, {}
+                for name, X in te.extra.items():
+                    a, b = X.A.numel(), X.B.numel()
+                    gx[name] = (self.flat_grad_p[o:o + a].view_as(X.A), self.flat_grad_p[o + a:o + a + b].view_as(X.B))
+                    o += a + b
+                self.grads_p += (gx,)
         self.vae = None  # attach_vae(): the step then starts from pixels (:1027-1037) instead of latents
         self.fused_tail = os.environ.get("TB_OPT_TAIL", "1") == "1"   # the optimizer tail as two launches (round 6) instead of ten
         self.opt_ws = torch.zeros(132, device=device)
@@ -309,6 +328,8 @@ class TextBoostStep:
         if hp.mixing is not None and te.r:  # :1119-1126 -- rows of each adapter's lora_B [D, r]: odd rows (object) / even rows (style) get no update
             gB = te.grad_B.view(te.geo.num_layers, 3, te.geo.hidden_size, te.r)
             gB[:, :, (1 if hp.mixing == "object" else 0)::2, :].zero_()
+            for X in te.extra.values():   # (the reference selects by the parameter name "lora_B": every adapted module's)
+                X.grad_B[:, (1 if hp.mixing == "object" else 0)::2, :].zero_()
 
     def _forward_backward_split(self):
         """the step body with the text encoder split over three branches (see `split_te` in __init__)"""
@@ -350,6 +371,8 @@ class TextBoostStep:
         if hp.mixing is not None and te.r:  # :1119-1126
             gB = te.grad_B.view(te.geo.num_layers, 3, te.geo.hidden_size, te.r)
             gB[:, :, (1 if hp.mixing == "object" else 0)::2, :].zero_()
+            for X in te.extra.values():   # (the reference selects by the parameter name "lora_B": every adapted module's)
+                X.grad_B[:, (1 if hp.mixing == "object" else 0)::2, :].zero_()
 
     def forward_backward(self):
         if self.split_te:
