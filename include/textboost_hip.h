@@ -416,6 +416,24 @@ int tb_lora_wide_pack(const float* A, const float* Bcat, void* a_pad, void* w2_f
 int tb_lora_wide_wgrad(const void* dY, int64_t lddy, const void* x, int64_t ldx, const void* t, int64_t ldt, const void* dt, int64_t lddt,
                        float* dA /* += */, float* dB /* += */, int64_t M, int D, int K, int r, int rp, int P, float scaling,
                        tb_stream_t stream);
+/* DoRA (--use_dora, peft 0.13.2 DoraLinearLayer; csrc/dora.hip): a learned magnitude m per output row on top of the adapter's direction.
+   `dtype` is the operand type of the mode (TB_F16: the build's 16-bit type, TB_F32: the fp32 mode).  fp32 sums in a fixed order, no atomics.
+   tb_dora_norms, all layers of one module in one launch (N = P*D rows, adapter p owns rows [p*D, (p+1)*D)):
+     n[l][j] = || W[l][j, :] + scaling * (B[l] A[l])[j, :] ||_2        c[l][j] = m[l][j] / n[l][j]   (c_out / m may both be NULL)
+   Wp: DEVICE array of `layers` pointers to the stored weights [N, K] (pitch K); A fp32 [layers][P*r, K], Bcat fp32 [layers][N, r];
+   D % 16 == 0, K % 2 == 0, 1 <= r <= 64. */
+int tb_dora_norms(const void* const* Wp, int dtype, const float* A, const float* Bcat, const float* m, float* n_out, float* c_out, int D,
+                  int K, int r, int P, int layers, float scaling, tb_stream_t stream);
+/* behind the GEMM that wrote u = x W^T + scaling (x A^T) B^T (no bias): v = c[n] * u[i, n] + bias[n] for rows i < Ms, u[i, n] + bias[n] for the
+   frozen rows Ms <= i < M (they never see c); then tb_gemm's epilogue: act NONE: y = v + R (R fp32 or NULL; y in `dtype` or fp32);
+   act QUICK_GELU / GELU: pre = v rounded to `dtype` (stored when pre != NULL), y = act(pre) in `dtype`.
+   N % 8 == 0, 16-byte aligned bases, pitches a multiple of 16 bytes. */
+int tb_dora_apply(const void* u, int64_t ldu, int dtype, const float* c, const float* bias, int64_t M, int64_t Ms, int N, int act,
+                  const float* R, int64_t ldr, void* y, int64_t ldy, int y_dtype, void* pre, int64_t ldpre, tb_stream_t stream);
+/* dU[i, n] = dY[i, n] * c[n] (in `dtype`) and dm[n] += (1 / nrm[n]) * sum_i dY[i, n] * u[i, n]: one workgroup per 64 columns walks all M rows.
+   Same shape rules as tb_dora_apply. */
+int tb_dora_bwd(const void* dY, int64_t lddy, const void* u, int64_t ldu, int dtype, const float* c, const float* nrm, void* dU, int64_t lddu,
+                float* dm /* += */, int64_t M, int N, tb_stream_t stream);
 
 /* ---- optimizer tail: all scalars stay on the device in `state` (fp32[TB_ST_COUNT]) ------------------- */
 enum { TB_ST_LOSS_SCALE = 0, TB_ST_GROWTH_TRACKER = 1, TB_ST_STEP = 2, TB_ST_FOUND_INF = 3, TB_ST_COEF_LORA = 4,

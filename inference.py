@@ -72,6 +72,9 @@ def load_runs(args):
     if len(runs) == 1 and args.weights is None:
         return runs[0]
     weights = args.weights or [1.0] * len(runs)
+    for run in runs:
+        if run.use_dora:   # (refused before the per-run report below reads its adapter)
+            raise SystemExit(f"inference.py: --with / --weights: {run.path} is a use_dora run, which does not compose; sample it on its own")
     for run, w in zip(runs, weights):
         print(f"run {run.path}: rank {run.rank}, lora_B rows {C.adapter_support(run)}, weight {w:g}, UNet K/V adapters "
               f"{'rank ' + str(run.unet_rank) if run.unet_rank else 'none'}")

@@ -189,6 +189,9 @@ _SIGS = {
     "tb_lora_set_variant": ([_I], C.c_int),
     "tb_lora_wide_pack": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP], C.c_int),
     "tb_lora_wide_wgrad": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _I, _I, _I, _I, _I, _F, _VP], C.c_int),
+    "tb_dora_norms": ([_VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _VP], C.c_int),
+    "tb_dora_apply": ([_VP, _I64, _I, _VP, _VP, _I64, _I64, _I, _I, _VP, _I64, _VP, _I64, _I, _VP, _I64, _VP], C.c_int),
+    "tb_dora_bwd": ([_VP, _I64, _VP, _I64, _I, _VP, _VP, _VP, _I64, _VP, _I64, _I, _VP], C.c_int),
     "tb_boundary_conv_set_variant": ([_I], C.c_int),
     "tb_lora_bwd": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _I64, _I, _I, _I, _I, _F, _VP], C.c_int),
     "tb_sumsq": ([_VP, _I64, _VP, _VP, _VP], C.c_int),

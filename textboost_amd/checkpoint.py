@@ -4,6 +4,8 @@ eval_dreambooth.py:193-206 / :329-337 read the results unchanged:
   <out>/text_encoder/adapter_config.json + adapter_model.safetensors     PEFT LoRA adapter, fp32, keys
         base_model.model.text_model.encoder.layers.{i}.self_attn.{q,k,v}_proj.lora_{A,B}.weight
         (+ ...self_attn.out_proj / ...mlp.fc1 / ...mlp.fc2 for the modules --lora_target_modules adds)
+        (+ <module>.lora_magnitude_vector, fp32 [N], for every adapted module of a --use_dora run: peft strips the adapter name and the
+         trailing `.weight` of `lora_magnitude_vector.default.weight` on save)
   <out>/{tok}.bin                                                        torch.save({"<tok>": tensor}); placeholder tokens save a
         1-D [D] row (:1189-1193), augmentation tokens a 2-D [1, D] slice (:1201-1205); '<' '>' stripped from the FILE name only
   <out>/checkpoint-{step}/ (same two things) + trainer state: model.safetensors, optimizer.bin, scheduler.bin, scaler.pt,
@@ -35,6 +37,17 @@ def lora_target_modules(te):
     return ["q_proj", "k_proj", "v_proj"] + list(_extra(te))
 
 
+DORA_KEY = ".lora_magnitude_vector"
+
+
+def uses_dora(te) -> bool:
+    return bool(getattr(te, "use_dora", False)) and te.r > 0
+
+
+def has_dora_tensors(sd) -> bool:
+    return any(k.endswith(DORA_KEY) for k in sd)
+
+
 def lora_state_dict(te) -> Dict[str, torch.Tensor]:
     """flat [L,3r,D] / [L,3D,r] masters -> PEFT key layout (adapter name stripped on save, like peft does)."""
     sd = {}
@@ -46,10 +59,14 @@ def lora_state_dict(te) -> Dict[str, torch.Tensor]:
             base = f"base_model.model.text_model.encoder.layers.{i}.self_attn.{name}"
             sd[base + ".lora_A.weight"] = te.lora_A[i, p * r:(p + 1) * r].detach().float().cpu().contiguous()
             sd[base + ".lora_B.weight"] = te.lora_B[i, p * D:(p + 1) * D].detach().float().cpu().contiguous()
+            if uses_dora(te):
+                sd[base + DORA_KEY] = te.mag[i, p * D:(p + 1) * D].detach().float().cpu().contiguous()
         for name, X in _extra(te).items():
             base = f"base_model.model.text_model.encoder.layers.{i}.{EXTRA_MODULE_PATH[name]}"
             sd[base + ".lora_A.weight"] = X.A[i].detach().float().cpu().contiguous()
             sd[base + ".lora_B.weight"] = X.B[i].detach().float().cpu().contiguous()
+            if uses_dora(te):
+                sd[base + DORA_KEY] = X.mag[i].detach().float().cpu().contiguous()
     return sd
 
 
@@ -62,10 +79,14 @@ def load_lora_state_dict(te, sd):
             base = f"base_model.model.text_model.encoder.layers.{i}.self_attn.{name}"
             te.lora_A[i, p * r:(p + 1) * r].copy_(sd[base + ".lora_A.weight"])
             te.lora_B[i, p * D:(p + 1) * D].copy_(sd[base + ".lora_B.weight"])
+            if uses_dora(te):
+                te.mag[i, p * D:(p + 1) * D].copy_(sd[base + DORA_KEY])
         for name, X in _extra(te).items():
             base = f"base_model.model.text_model.encoder.layers.{i}.{EXTRA_MODULE_PATH[name]}"
             X.A[i].copy_(sd[base + ".lora_A.weight"])
             X.B[i].copy_(sd[base + ".lora_B.weight"])
+            if uses_dora(te):
+                X.mag[i].copy_(sd[base + DORA_KEY])
 
 
 def unet_lora_state_dict(unet) -> Dict[str, torch.Tensor]:
@@ -135,21 +156,21 @@ def save_unet_adapters(unet, out_dir: str, base_model_name_or_path: str):
                 "and unchanged: load them from <base_model_name_or_path>/unet.\n")
 
 
-def adapter_config(rank: int, base_model_name_or_path: str, target_modules=("q_proj", "k_proj", "v_proj")) -> dict:
+def adapter_config(rank: int, base_model_name_or_path: str, target_modules=("q_proj", "k_proj", "v_proj"), use_dora: bool = False) -> dict:
     """peft 0.13.2 LoraConfig JSON for LoraConfig(r, lora_alpha=r, init_lora_weights="gaussian", target q/k/v) (:702-709); target_modules: the
-    trained list of --lora_target_modules."""
+    trained list of --lora_target_modules; use_dora: a --use_dora run (LoraConfig(use_dora=True))."""
     return {"alpha_pattern": {}, "auto_mapping": None, "base_model_name_or_path": base_model_name_or_path, "bias": "none",
             "fan_in_fan_out": False, "inference_mode": True, "init_lora_weights": "gaussian", "layer_replication": None,
             "layers_pattern": None, "layers_to_transform": None, "loftq_config": {}, "lora_alpha": rank, "lora_dropout": 0.0,
             "megatron_config": None, "megatron_core": "megatron.core", "modules_to_save": None, "peft_type": "LORA", "r": rank,
             "rank_pattern": {}, "revision": None, "target_modules": list(target_modules), "task_type": None,
-            "use_dora": False, "use_rslora": False}
+            "use_dora": bool(use_dora), "use_rslora": False}
 
 
 def save_text_encoder_adapter(te, out_dir: str, base_model_name_or_path: str):
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "adapter_config.json"), "w") as f:
-        json.dump(adapter_config(te.r, base_model_name_or_path, lora_target_modules(te)), f, indent=2, sort_keys=True)
+        json.dump(adapter_config(te.r, base_model_name_or_path, lora_target_modules(te), uses_dora(te)), f, indent=2, sort_keys=True)
     save_file(lora_state_dict(te), os.path.join(out_dir, "adapter_model.safetensors"), metadata={"format": "pt"})
 
 

@@ -90,6 +90,11 @@ EXTENSION_FLAGS = [
     # its target_modules line (train_textboost.py:706)
     ("--lora_target_modules", dict(type="str", nargs="+", default=["q_proj", "k_proj", "v_proj"], choices=LORA_TARGET_CHOICES, metavar="M")),
 ]
+# the adapter's variants (also not the reference's).  --use_dora: peft's LoraConfig(use_dora=True) -- every adapted Linear also trains a magnitude
+# per output row; needs --lora_rank > 0
+ADAPTER_VARIANT_FLAGS = [
+    ("--use_dora", dict(action="store_true", default=False)),
+]
 
 
 def flag_table():
@@ -104,7 +109,7 @@ def flag_table():
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="TextBoost training on MI355X (HIP kernels behind the reference CLI).")
-    for name, kw in FLAGS + EXTENSION_FLAGS:
+    for name, kw in FLAGS + EXTENSION_FLAGS + ADAPTER_VARIANT_FLAGS:
         kw = dict(kw)
         if "type" in kw:
             kw["type"] = _T[kw["type"]]
@@ -131,4 +136,6 @@ def parse_args(input_args=None):
     if missing:  # q/k/v are one three-adapter kernel set, and the reference always trains them
         raise ValueError(f"--lora_target_modules must contain q_proj k_proj v_proj; {' '.join(missing)} missing")
     args.lora_target_modules = [m for m in LORA_TARGET_CHOICES if m in args.lora_target_modules]   # canonical order, duplicates dropped
+    if args.use_dora and args.lora_rank <= 0:
+        raise ValueError("--use_dora needs --lora_rank > 0: DoRA decomposes the adapted weight, and --lora_rank 0 injects no adapter")
     return args

@@ -28,9 +28,16 @@ def _proj(m) -> str:
     return m.group("proj") or m.group("fc")
 
 
+def _refuse_dora(run: TrainedRun):
+    if getattr(run, "use_dora", False):
+        raise NotImplementedError(f"compose_runs: {run.path} is a use_dora run: DoRA renormalises every row of W + B A, so adapters do not add (or "
+                                  "scale) by rank concatenation; sample it on its own, without --with / --weights")
+
+
 def _modules(run: TrainedRun) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
     """module name (`...layers.{i}.self_attn.{q,k,v,out}_proj`, `...layers.{i}.mlp.fc{1,2}`) -> (lora_A [r, K], lora_B [N, r]); a key of any
     other form is refused"""
+    _refuse_dora(run)
     halves: Dict[str, Dict[str, torch.Tensor]] = {}
     for k, v in run.lora.items():
         m = _KEY.match(k)
@@ -91,10 +98,13 @@ def compose_runs(runs: Sequence[TrainedRun], weights: Optional[Sequence[float]] 
     UNet       the cross-attention K/V adapters of all runs, composed the same way (`unet_rank` = the sum of their ranks)
     path, files   the first run's
     Refused: ValueError when the runs disagree in hidden size, layer count or adapter key set, or `weights` has another length than `runs`;
-    NotImplementedError when the ranks add up to more than the adapter kernels take."""
+    NotImplementedError when the ranks add up to more than the adapter kernels take, or when a run is a DoRA one (use_dora): its rows are
+    renormalised by || W + B A ||, which is not additive in the adapters, so rank concatenation does not define the sum."""
     runs = list(runs)
     if not runs:
         raise ValueError("compose_runs: no run given")
+    for run in runs:
+        _refuse_dora(run)
     weights = [1.0] * len(runs) if weights is None else [float(w) for w in weights]
     if len(weights) != len(runs):
         raise ValueError(f"compose_runs: {len(weights)} weights for {len(runs)} runs")

@@ -40,11 +40,12 @@ HUB_ALIASES = ("sd14", "sd15", "sd21base", "sd21")     # eval_dreambooth.py:18-2
 SKIPPED_BIN = ("optimizer.bin", "scheduler.bin")       # :199-206
 LORA_TARGETS = ("q_proj", "k_proj", "v_proj")
 LORA_EXTRA_TARGETS = ("out_proj", "fc1", "fc2")     # --lora_target_modules may add these (text_encoder.LORA_EXTRA)
+DORA_KEY = ".lora_magnitude_vector"                 # <module>.lora_magnitude_vector of a --use_dora run (checkpoint.DORA_KEY)
 
 
 def lora_targets_of(lora) -> Tuple[str, ...]:
     """the adapted modules of a peft adapter state dict (`...{self_attn,mlp}.<module>.lora_{A,B}.weight`), q/k/v first"""
-    held = {k.split(".")[-3] for k in lora}
+    held = {k.split(".")[-3] for k in lora if not k.endswith(DORA_KEY)}
     return tuple(n for n in LORA_TARGETS + LORA_EXTRA_TARGETS if n in held)
 UNET_LORA_TARGETS = ("attn2.to_k", "attn2.to_v")      # checkpoint.save_unet_adapters
 MAX_PNG_THREADS = 8
@@ -143,6 +144,7 @@ class TrainedRun:
     unet_rank: int = 0                                  # <path>/unet/: rank of the cross-attention K/V adapters (0: none)
     unet_lora: Dict[str, torch.Tensor] = field(default_factory=dict)       # in-model keys (checkpoint.unet_lora_state_dict)
     shadowed: List[Tuple[str, str]] = field(default_factory=list)          # compose.compose_runs: (token, path of the run whose vector was dropped)
+    use_dora: bool = False                              # a --use_dora run: `lora` also holds <module>.lora_magnitude_vector, fp32 [N]
 
 
 def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedRun:
@@ -156,12 +158,13 @@ def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedR
     with open(os.path.join(te_dir, "adapter_config.json")) as f:
         cfg = json.load(f)
     r = int(cfg.get("r", 0))
-    if cfg.get("use_dora"):
-        raise NotImplementedError(f"{te_dir}: use_dora adapters are not built")
+    use_dora = bool(cfg.get("use_dora"))
     if cfg.get("use_rslora"):
         raise NotImplementedError(f"{te_dir}: use_rslora adapters are not built (scaling alpha / sqrt(r))")
     if r and cfg.get("lora_alpha", r) != r:
         raise NotImplementedError(f"{te_dir}: lora_alpha = {cfg.get('lora_alpha')} != r = {r}: the kernels carry no separate LoRA scaling")
+    if use_dora and not r:
+        raise NotImplementedError(f"{te_dir}: use_dora with r = 0: there is no adapter to decompose")
     if r > MAX_LORA_RANK:
         raise NotImplementedError(f"{te_dir}: rank-{r} adapters are not built (the text-encoder adapter kernels take r <= {MAX_LORA_RANK})")
     targets = cfg.get("target_modules") or []
@@ -171,7 +174,15 @@ def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedR
                                   "and, beside them, out_proj / fc1 / fc2")
     lora = load_file(os.path.join(te_dir, "adapter_model.safetensors")) if r else {}
     if r:
-        held = {k.split(".")[-3] for k in lora}
+        mags = {k: v for k, v in lora.items() if k.endswith(DORA_KEY)}
+        if use_dora and not mags:   # (the magnitudes are what makes the adapter a DoRA one: without them only a plain LoRA could run, silently)
+            raise NotImplementedError(f"{te_dir}: use_dora is set, but adapter_model.safetensors holds no lora_magnitude_vector tensors")
+        if mags and not use_dora:
+            raise NotImplementedError(f"{te_dir}: adapter_model.safetensors holds lora_magnitude_vector tensors, but use_dora is not set")
+        held = {k.split(".")[-3] for k in lora if k not in mags}
+        if use_dora and {k.split(".")[-2] for k in mags} != held:
+            raise NotImplementedError(f"{te_dir}: use_dora: lora_magnitude_vector tensors of {sorted({k.split('.')[-2] for k in mags})}, "
+                                      f"adapters of {sorted(held)}")
         if held != set(targets):   # (a listed module without tensors would silently run un-adapted; tensors of an unlisted one would be dropped)
             raise NotImplementedError(f"{te_dir}: target_modules {sorted(targets)}, but adapter_model.safetensors holds tensors of {sorted(held)}")
         a = [v for k, v in lora.items() if k.endswith("lora_A.weight")]
@@ -197,7 +208,7 @@ def read_run_dir(model_path: str, hidden_size: Optional[int] = None) -> TrainedR
         names = [tok] + [f"{tok}_{i}" for i in range(1, t.shape[0])]    # diffusers load_textual_inversion: tok, tok_1, ..., tok_{n-1}
         tokens += [(n, t[i].clone()) for i, n in enumerate(names)]
     unet_rank, unet_lora = read_unet_adapters(model_path)
-    return TrainedRun(path=model_path, rank=r, lora=lora, tokens=tokens, files=files, unet_rank=unet_rank, unet_lora=unet_lora)
+    return TrainedRun(path=model_path, rank=r, lora=lora, tokens=tokens, files=files, unet_rank=unet_rank, unet_lora=unet_lora, use_dora=use_dora)
 
 
 def read_unet_adapters(model_path: str) -> Tuple[int, Dict[str, torch.Tensor]]:
@@ -284,7 +295,7 @@ def load_text_encoder(model_dir: str, run: TrainedRun, batch: int, device="cuda"
     from transformers import CLIPTokenizer
     tokenizer = CLIPTokenizer.from_pretrained(tdir, local_files_only=True)     # (train_textboost.load_tokenizer)
     te = HipTextEncoder(geo, base.state_dict, batch, mode="autocast", lora_rank=run.rank, device=device,
-                        lora_targets=lora_targets_of(run.lora) if run.rank else None)
+                        lora_targets=lora_targets_of(run.lora) if run.rank else None, **({"use_dora": True} if run.use_dora else {}))
     if run.rank:
         ckpt.load_lora_state_dict(te, run.lora)
         te.pack_lora()

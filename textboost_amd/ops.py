@@ -885,6 +885,55 @@ def lora_bwd(dY, x, t, Bcat, dt, dA, dB, D, K, r, P, scaling=1.0, ws=None, w2_fw
                                 dt.stride(0), L.ptr(dA), L.ptr(dB), L.ptr(ws), M, D, K, r, P, scaling, L.stream()), "tb_lora_bwd")
 
 
+# ------------------------------------------------------------------ DoRA (csrc/dora.hip)
+def dora_weight_ptrs(weights):
+    """device array of the stored weights' addresses, one per layer (`Wp` of tb_dora_norms); the caller keeps `weights` alive"""
+    w0 = weights[0]
+    for w in weights:
+        assert w.is_contiguous() and w.shape == w0.shape and w.dtype == w0.dtype and w.device == w0.device
+    return torch.tensor([w.data_ptr() for w in weights], dtype=torch.int64, device=w0.device)
+
+
+def dora_norms(w_ptrs, w_dtype, A, Bcat, m, n_out, c_out, D, K, r, P, scaling=1.0, layers=1):
+    """tb_dora_norms: n_out [layers, P*D] = row norms of W + scaling * B A over all layers of one module, c_out = m / n_out (m, c_out: both or
+    neither).  W [P*D, K] of layer l at address w_ptrs[l] in `w_dtype`; A [layers][P*r, K], Bcat [layers][P*D, r] fp32."""
+    N = P * D
+    assert w_ptrs.dtype == torch.int64 and w_ptrs.numel() == layers and w_ptrs.is_cuda
+    assert A.is_contiguous() and Bcat.is_contiguous() and A.dtype == torch.float32 and Bcat.dtype == torch.float32
+    assert A.numel() == layers * P * r * K and Bcat.numel() == layers * N * r
+    assert (m is None) == (c_out is None)
+    for o in (n_out,) + (() if m is None else (m, c_out)):
+        assert o.is_contiguous() and o.dtype == torch.float32 and o.numel() == layers * N
+    dt = L.TB_F32 if w_dtype == torch.float32 else L.TB_F16
+    assert dt == L.TB_F32 or w_dtype == L.half_dtype()
+    L.check(L.lib().tb_dora_norms(L.ptr(w_ptrs), dt, L.ptr(A), L.ptr(Bcat), L.ptr(m), L.ptr(n_out), L.ptr(c_out), D, K, r, P, layers, scaling,
+                                  L.stream()), "tb_dora_norms")
+
+
+def dora_apply(u, c, bias, out, rows, act=L.ACT_NONE, R=None, pre=None):
+    """tb_dora_apply: out = epilogue(c * u + bias) on rows < `rows`, epilogue(u + bias) on the frozen rows behind them (R: fp32 residual;
+    act QUICK_GELU / GELU with `pre` = the saved pre-activation)."""
+    M, N = u.shape
+    assert out.shape == (M, N) and u.stride(1) == 1 and out.stride(1) == 1 and c.numel() == N and bias.numel() == N
+    assert c.dtype == torch.float32 and bias.dtype == torch.float32 and c.is_contiguous() and bias.is_contiguous()
+    assert R is None or (R.dtype == torch.float32 and R.shape == (M, N) and R.stride(1) == 1)
+    assert pre is None or (pre.dtype == u.dtype and pre.shape == (M, N) and pre.stride(1) == 1)
+    L.check(L.lib().tb_dora_apply(L.ptr(u), u.stride(0), _dt(u), L.ptr(c), L.ptr(bias), M, rows, N, act, L.ptr(R), R.stride(0) if R is not None else 0,
+                                  L.ptr(out), out.stride(0), _dt(out), L.ptr(pre), pre.stride(0) if pre is not None else 0, L.stream()),
+            "tb_dora_apply")
+
+
+def dora_bwd(dY, u, c, n, dU, dm):
+    """tb_dora_bwd: dU = dY * c (operand dtype), dm += colsum(dY * u) / n (fp32, fixed order)."""
+    M, N = dY.shape
+    assert u.shape == (M, N) and dU.shape == (M, N) and dY.dtype == u.dtype == dU.dtype
+    assert dY.stride(1) == 1 and u.stride(1) == 1 and dU.stride(1) == 1
+    for o in (c, n, dm):
+        assert o.dtype == torch.float32 and o.is_contiguous() and o.numel() == N
+    L.check(L.lib().tb_dora_bwd(L.ptr(dY), dY.stride(0), L.ptr(u), u.stride(0), _dt(u), L.ptr(c), L.ptr(n), L.ptr(dU), dU.stride(0), L.ptr(dm),
+                                M, N, L.stream()), "tb_dora_bwd")
+
+
 # ------------------------------------------------------------------ optimizer tail
 _sumsq_ws = {}
 

@@ -13,6 +13,9 @@ Three numeric modes, matching how the reference runs the two encoders (SURVEY.md
 
 `lora_targets` (--lora_target_modules) may add out_proj / fc1 / fc2 to q/k/v: one adapter each (P = 1) on a 64-column K-extension of its own,
 masters in `extra[name].A [L, r, K_in]` / `.B [L, D_out, r]`.
+`use_dora` (--use_dora) adds a magnitude per output row of every adapted Linear, `mag [L, 3D]` / `extra[name].mag [L, D_out]`: the GEMM then writes
+u = x W^T + (x A^T) B^T, `tb_dora_apply` scales the student rows by m / ||W + B A|| and runs the Linear's epilogue, `tb_dora_bwd` turns dY into dU
+and adds the magnitude gradient (csrc/dora.hip).
 
 All arithmetic is in libtextboost_hip.so; this file owns parameters, buffers and the layer schedule.
 Trainable state lives in three flat fp32 buffers so the optimizer / all-reduce see one tensor each:
@@ -73,10 +76,16 @@ HF_LAYER = {"ln1": "layer_norm1", "ln2": "layer_norm2", "q": "self_attn.q_proj",
 class HipTextEncoder:
     def __init__(self, geo: CLIPGeometry, state_dict: Dict[str, torch.Tensor], batch: int, mode: str = "autocast", lora_rank: int = 0,
                  lora_alpha: Optional[float] = None, n_slots: int = 1, device="cuda", seed: Optional[int] = None,
-                 lora_targets: Optional[Sequence[str]] = None):
-        """state_dict uses transformers CLIPTextModel keys (`text_model.embeddings.token_embedding.weight`, ...)."""
+                 lora_targets: Optional[Sequence[str]] = None, use_dora: bool = False):
+        """state_dict uses transformers CLIPTextModel keys (`text_model.embeddings.token_embedding.weight`, ...).
+        use_dora (--use_dora): every adapted Linear also trains a magnitude per output row: `mag` [L, 3D] for q/k/v and
+        `extra[name].mag` [L, D_out], initialised to the stored weights' row norms."""
         assert mode in ("autocast", "half", "fp32")
         assert geo.act in ("quick_gelu", "gelu")  # SD1.x CLIP-L / SD2.x OpenCLIP-H
+        if use_dora and not lora_rank:
+            raise ValueError("use_dora needs a LoRA adapter (lora_rank > 0)")
+        if use_dora and mode == "half":
+            raise NotImplementedError("use_dora: the adapted encoder runs in the autocast and fp32 modes")
         self.act_fwd, self.act_bwd = (L.ACT_QUICK_GELU, L.ACT_QUICK_GELU_GRAD) if geo.act == "quick_gelu" else (L.ACT_GELU, L.ACT_GELU_GRAD)
         self.geo, self.B, self.T, self.mode, self.dev = geo, batch, geo.max_pos, mode, device
         self.r = lora_rank
@@ -122,6 +131,7 @@ class HipTextEncoder:
         self.wide = False
         self.extra: Dict[str, SimpleNamespace] = {}
         self.lora_targets = LORA_QKV + check_lora_targets(lora_targets)
+        self.use_dora = bool(use_dora)
         if self.r > ops.LORA_MAX_RANK:
             raise NotImplementedError(f"text-encoder LoRA rank {self.r}: ranks up to {ops.LORA_MAX_RANK} are supported")
         if self.r:
@@ -157,6 +167,42 @@ class HipTextEncoder:
                 X.w2_dgrad = torch.zeros(Lr, Kin, 64, device=device, dtype=odt)
                 X.w2_t = None if mode == "fp32" else torch.zeros(Lr, 64, Dout, device=device, dtype=odt)   # weight of the dt GEMM
                 self.extra[name] = X
+            if self.use_dora:
+                self._init_dora()
+
+    # ------------------------------------------------------------------ DoRA (csrc/dora.hip)
+    def _dora_of(self, name):
+        """holder of a module's magnitude state (`mag`, `grad_mag`, `dora_n`, `dora_c`, `dora_wp`): the encoder itself for "qkv" (the P = 3 stack)"""
+        return self if name == "qkv" else self.extra[name]
+
+    def dora_modules(self):
+        return ("qkv",) + tuple(self.extra) if self.use_dora else ()
+
+    def _init_dora(self):
+        """magnitudes m = ||W_j|| of the stored (operand-dtype) weights: the norm kernel with B = 0, which it is here"""
+        Lr, D = self.geo.num_layers, self.geo.hidden_size
+        for name in self.dora_modules():
+            H = self._dora_of(name)
+            N = 3 * D if name == "qkv" else H.D
+            H.dora_w = [W[("qkv" if name == "qkv" else H.w) + ".w"] for W in self.Wl]
+            H.dora_wp = ops.dora_weight_ptrs(H.dora_w)
+            H.mag = torch.zeros(Lr, N, device=self.dev)
+            H.grad_mag = torch.zeros_like(H.mag)
+            H.dora_n = torch.zeros_like(H.mag)      # n = ||W + s B A|| per row and c = m / n, refreshed by pack_lora()
+            H.dora_c = torch.ones_like(H.mag)
+        self._dora_norms(init=True)
+
+    def _dora_norms(self, init=False):
+        D = self.geo.hidden_size
+        for name in self.dora_modules():
+            H = self._dora_of(name)
+            A, B, Dn, K, P = (self.lora_A, self.lora_B, D, D, 3) if name == "qkv" else (H.A, H.B, H.D, H.K, 1)
+            if init:
+                ops.dora_norms(H.dora_wp, self.op_dtype, A, torch.zeros_like(B), None, H.mag, None, Dn, K, self.r, P, self.scaling,
+                               layers=self.geo.num_layers)
+            else:
+                ops.dora_norms(H.dora_wp, self.op_dtype, A, B, H.mag, H.dora_n, H.dora_c, Dn, K, self.r, P, self.scaling,
+                               layers=self.geo.num_layers)
 
     # ------------------------------------------------------------------ reference-facing surface
     def set_null_embedding(self, null):  # text_encoder.py:28-32
@@ -206,8 +252,10 @@ class HipTextEncoder:
         if self.wide:
             ops.lora_wide_pack(self.lora_A, self.lora_B, self.a_pad, self.w2_fwd, self.w2_t, self.w2_dgrad, D, D, self.r, self.rp, 3, self.scaling,
                                layers=self.geo.num_layers)
-            return
-        ops.lora_pack(self.lora_A, self.lora_B, self.w2_fwd, self.w2_dgrad, D, D, self.r, 3, self.scaling, layers=self.geo.num_layers)
+        else:
+            ops.lora_pack(self.lora_A, self.lora_B, self.w2_fwd, self.w2_dgrad, D, D, self.r, 3, self.scaling, layers=self.geo.num_layers)
+        if self.use_dora:   # one launch per module: the row norms of W + s B A from the fp32 masters, and c = m / n
+            self._dora_norms()
 
     # ------------------------------------------------------------------ forward
     def forward(self, input_ids, slot=0, pins=True, extra_ids=None, extra_table=None):
@@ -229,6 +277,16 @@ class HipTextEncoder:
         self._bufs[s + "ids"] = ids
         xl = self.extra
         gemm_down = self.wide or full32   # the down projection as a GEMM on a_pad; else tb_lora_down / the LayerNorm launch, on the fp32 masters
+        dora = self.use_dora
+
+        def linear(name, p, i, xin, w, out, A2, W2, bias, R=None, act=L.ACT_NONE, C2=None):
+            """an adapted Linear.  DoRA: the GEMM writes u = x W^T + s (x A^T) B^T (kept per layer for the backward), then tb_dora_apply scales the
+            student rows' columns by c = m / n, adds the bias and runs the Linear's own epilogue; the frozen rows behind them take no scale"""
+            if not dora:
+                return ops.gemm(xin, w, out, A2=A2, W2=W2, bias=bias, R=R, act=act, C2=C2)
+            u = self.buf(p + "u_" + name, M, w.shape[0], f16)
+            ops.gemm(xin, w, u, A2=A2, W2=W2)
+            ops.dora_apply(u, self._dora_of(name).dora_c[i], bias, out, Ms, act=act, R=R, pre=C2)
 
         def down(name, xin, p, i):
             """t [M, 64] of an extra adapter: rows < Ms = xin @ A^T in columns [0, r); padding columns and the frozen extra rows stay zero"""
@@ -259,7 +317,7 @@ class HipTextEncoder:
                     ops.gemm(x1[:Ms], self.lora_A[i], t[:Ms, :3 * self.r])
                 else:
                     ops.layernorm_fwd(h, x1, W["ln1.g"], W["ln1.b"], ls1, geo.eps, lora_A=self.lora_A[i], t=t, lora_rows=Ms)
-                ops.gemm(x1, W["qkv.w"], qkv, A2=t, W2=self.w2_fwd[i], bias=W["qkv.b"])
+                linear("qkv", p, i, x1, W["qkv.w"], qkv, t, self.w2_fwd[i], W["qkv.b"])
             else:
                 ops.layernorm_fwd(h, x1, W["ln1.g"], W["ln1.b"], ls1, geo.eps)
                 ops.gemm(x1, W["qkv.w"], qkv, bias=W["qkv.b"])
@@ -268,7 +326,7 @@ class HipTextEncoder:
             ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], o, lse, B, H, T, T, hd, causal=True)
             h2 = self.buf(p + "h2", M, D, rdt)
             if "out_proj" in xl:
-                ops.gemm(o, W["out.w"], h2, A2=down("out_proj", o, p, i), W2=xl["out_proj"].w2_fwd[i], bias=W["out.b"], R=h)
+                linear("out_proj", p, i, o, W["out.w"], h2, down("out_proj", o, p, i), xl["out_proj"].w2_fwd[i], W["out.b"], R=h)
             else:
                 ops.gemm(o, W["out.w"], h2, bias=W["out.b"], R=h)
             # (an adapted fc1 / fc2 needs its input again in the backward, for dA = dt^T x: that layer input is then kept per layer)
@@ -283,13 +341,13 @@ class HipTextEncoder:
                 else:   # the down projection rides in the LayerNorm launch, as q/k/v's does in LayerNorm 1
                     t1 = self.buf(p + "t_fc1", M, 64, f16)
                     ops.layernorm_fwd(h2, x2, W["ln2.g"], W["ln2.b"], ls2, geo.eps, lora_A=xl["fc1"].A[i], t=t1, lora_rows=Ms)
-                ops.gemm(x2, W["fc1.w"], a, A2=t1, W2=xl["fc1"].w2_fwd[i], bias=W["fc1.b"], act=self.act_fwd, C2=pre)
+                linear("fc1", p, i, x2, W["fc1.w"], a, t1, xl["fc1"].w2_fwd[i], W["fc1.b"], act=self.act_fwd, C2=pre)
             else:
                 ops.layernorm_fwd(h2, x2, W["ln2.g"], W["ln2.b"], ls2, geo.eps)
                 ops.gemm(x2, W["fc1.w"], a, bias=W["fc1.b"], act=self.act_fwd, C2=pre)
             h3 = self.buf(p + "h3", M, D, rdt)
             if "fc2" in xl:
-                ops.gemm(a, W["fc2.w"], h3, A2=down("fc2", a, p, i), W2=xl["fc2"].w2_fwd[i], bias=W["fc2.b"], R=h2)
+                linear("fc2", p, i, a, W["fc2.w"], h3, down("fc2", a, p, i), xl["fc2"].w2_fwd[i], W["fc2.b"], R=h2)
             else:
                 ops.gemm(a, W["fc2.w"], h3, bias=W["fc2.b"], R=h2)
             h = h3
@@ -310,6 +368,8 @@ class HipTextEncoder:
             for X in self.extra.values():
                 X.grad_A.zero_()
                 X.grad_B.zero_()
+            for name in self.dora_modules():
+                self._dora_of(name).grad_mag.zero_()
         if self.n_added:
             self.grad_added.zero_()
 
@@ -322,8 +382,11 @@ class HipTextEncoder:
         grad_A, grad_B, grad_added = grads[:3] if grads is not None else (self.grad_A if self.r else None, self.grad_B if self.r else None,
                                                                           self.grad_added if self.n_added else None)
         xl = self.extra
-        assert grads is None or not xl or len(grads) == 4, "an encoder with extra adapted modules needs their gradient buffers too"
+        assert grads is None or not xl or len(grads) >= 4, "an encoder with extra adapted modules needs their gradient buffers too"
         grad_x = grads[3] if grads is not None and xl else {n: (X.grad_A, X.grad_B) for n, X in xl.items()}
+        # DoRA: grads = (grad_A, grad_B, grad_added, {extra module: (grad_A, grad_B)} or {}, {"qkv" | extra module: grad_mag})
+        assert grads is None or not self.use_dora or len(grads) == 5, "a DoRA encoder needs the magnitude gradient buffers too"
+        grad_m = grads[4] if grads is not None and self.use_dora else {n: self._dora_of(n).grad_mag for n in self.dora_modules()}
         full32 = self.mode == "fp32"
         geo, T = self.geo, self.T
         D, I, H = geo.hidden_size, geo.intermediate_size, geo.num_heads
@@ -347,6 +410,15 @@ class HipTextEncoder:
                 ops.lora_rect_bwd(dY, x, t_, X.w2_t[i], dt_, gA[i], gB[i], X.D, X.K, self.r, self.scaling)
             return dt_
 
+        def dora_bwd(name, i, dY):
+            """DoRA: dU = dY * c in dY's place for everything below (adapter gradients, dgrad); the magnitude gradient is added on the way"""
+            if name not in grad_m:
+                return dY
+            H = self._dora_of(name)
+            dU = self.buf(gs + f"du{dY.shape[1]}", M, dY.shape[1], f16)
+            ops.dora_bwd(dY, self._bufs[f"{s}l{i}.u_{name}"][:M], H.dora_c[i], H.dora_n[i], dU, grad_m[name][i])
+            return dU
+
         if pins:
             ops.pin_bwd(d_out, ids, B, T, self.use_fixed_special_embedding, EOS_ID)
         h_last = self._bufs[f"{s}l{geo.num_layers - 1}.h3"][:M]
@@ -367,11 +439,13 @@ class HipTextEncoder:
             dpre = self.buf(gs + "dpre", M, I, f16)
             dy = dh if full32 else dh16
             if "fc2" in xl:
+                dy = dora_bwd("fc2", i, dy)
                 ops.gemm(dy, W["fc2.wd"], dpre, A2=extra_bwd("fc2", i, dy, self._bufs[p + "a"][:M]), W2=xl["fc2"].w2_dgrad[i], act=self.act_bwd, C2=pre)
             else:
                 ops.gemm(dy, W["fc2.wd"], dpre, act=self.act_bwd, C2=pre)
             dx2 = self.buf(gs + "dx", M, D, f16)
             if "fc1" in xl:
+                dpre = dora_bwd("fc1", i, dpre)
                 ops.gemm(dpre, W["fc1.wd"], dx2, A2=extra_bwd("fc1", i, dpre, self._bufs[p + "x2"][:M]), W2=xl["fc1"].w2_dgrad[i])
             else:
                 ops.gemm(dpre, W["fc1.wd"], dx2)
@@ -380,6 +454,7 @@ class HipTextEncoder:
             do = self.buf(gs + "do", M, D, f16)
             dy = dh2 if full32 else dh16
             if "out_proj" in xl:
+                dy = dora_bwd("out_proj", i, dy)
                 ops.gemm(dy, W["out.wd"], do, A2=extra_bwd("out_proj", i, dy, o), W2=xl["out_proj"].w2_dgrad[i])
             else:
                 ops.gemm(dy, W["out.wd"], do)
@@ -389,6 +464,7 @@ class HipTextEncoder:
                               dqkv[:, 2 * D:], B, H, T, T, hd, causal=True)
             dx1 = self.buf(gs + "dx", M, D, f16)
             if self.r:
+                dqkv = dora_bwd("qkv", i, dqkv)
                 if self.wide:
                     dt = self.buf(gs + "dt", M, self.lw, f16)
                     if full32:

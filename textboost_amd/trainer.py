@@ -149,9 +149,15 @@ class TextBoostStep:
         # with the default list nothing moves
         extra = list(te.extra.values()) if has_lora else []
         nX = sum(X.A.numel() + X.B.numel() for X in extra)
-        self.flat_grad = torch.zeros(nA + nB + nX + nE + self.n_unet, device=device)
+        # --use_dora: the magnitude vectors are `text_model.encoder` parameters like the adapters (same group, lr, decay and clip); they lie behind
+        # the extra modules' tensors, [... | m_qkv | m_x per extra module | added rows | ...], so the moments, the all-reduce and the fused tail
+        # cover them through the flat views.  The --mixing mask stays on lora_B rows, as the reference defines it (:1119-1126 selects by name).
+        dora = [te._dora_of(n) for n in te.dora_modules()] if has_lora and getattr(te, "use_dora", False) else []
+        nM = sum(Md.mag.numel() for Md in dora)
+        self.flat_grad = torch.zeros(nA + nB + nX + nM + nE + self.n_unet, device=device)
         if has_lora:
-            self.flat_lora = torch.cat([te.lora_A.reshape(-1), te.lora_B.reshape(-1)] + [t.reshape(-1) for X in extra for t in (X.A, X.B)])  # fp32 masters, flat
+            self.flat_lora = torch.cat([te.lora_A.reshape(-1), te.lora_B.reshape(-1)] + [t.reshape(-1) for X in extra for t in (X.A, X.B)]
+                                       + [Md.mag.reshape(-1) for Md in dora])  # fp32 masters, flat
             te.lora_A = self.flat_lora[:nA].view_as(te.lora_A)
             te.lora_B = self.flat_lora[nA:nA + nB].view_as(te.lora_B)
             te.grad_A = self.flat_grad[:nA].view_as(te.lora_A)
@@ -162,9 +168,13 @@ class TextBoostStep:
                 X.A, X.grad_A = self.flat_lora[o:o + a].view_as(X.A), self.flat_grad[o:o + a].view_as(X.A)
                 X.B, X.grad_B = self.flat_lora[o + a:o + a + b].view_as(X.B), self.flat_grad[o + a:o + a + b].view_as(X.B)
                 o += a + b
+            for Md in dora:
+                n = Md.mag.numel()
+                Md.mag, Md.grad_mag = self.flat_lora[o:o + n].view_as(Md.mag), self.flat_grad[o:o + n].view_as(Md.mag)
+                o += n
         else:
             self.flat_lora = torch.zeros(0, device=device)
-        nBq, nB = nB, nB + nX   # (below, "nA + nB" is the end of the encoder's adapter block)
+        nBq, nB = nB, nB + nX + nM   # (below, "nA + nB" is the end of the encoder's adapter block)
         te.grad_added = self.flat_grad[nA + nB:nA + nB + nE].view(te.n_added, D)
         self.n_lora = nA + nB
         self.n_emb = nE
@@ -261,6 +271,13 @@ class TextBoostStep:
                     gx[name] = (self.flat_grad_p[o:o + a].view_as(X.A), self.flat_grad_p[o + a:o + a + b].view_as(X.B))
                     o += a + b
                 self.grads_p += (gx,)
+            if dora:
+                o, gm = nA + nBq + nX, {}
+                for name in te.dora_modules():
+                    n = te._dora_of(name).mag.numel()
+                    gm[name] = self.flat_grad_p[o:o + n].view_as(te._dora_of(name).mag)
+                    o += n
+                self.grads_p = self.grads_p[:3] + (self.grads_p[3] if extra else {}, gm)
         self.vae = None  # attach_vae(): the step then starts from pixels (:1027-1037) instead of latents
         self.fused_tail = os.environ.get("TB_OPT_TAIL", "1") == "1"   # the optimizer tail as two launches (round 6) instead of ten
         self.opt_ws = torch.zeros(132, device=device)

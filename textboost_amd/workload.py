@@ -34,7 +34,7 @@ def synthetic_ids(B, added_ids, gen: torch.Generator, prior=False, null_prob=0.1
 
 def build_step(batch=8, latent=64, unet_geo: UNetGeometry = models.SD15_UNET, clip_geo: CLIPGeometry = models.SD15_CLIP,
                lora_rank=4, n_added=18, hyper: StepHyper | None = None, weight_seed=1234, data_seed=1000, device="cuda",
-               world_size=1, with_vae=False, attn_fp8=False, precision="fp16", lora_targets=None):
+               world_size=1, with_vae=False, attn_fp8=False, precision="fp16", lora_targets=None, use_dora=False):
     """Config 2 of BASELINE.json by default: SD1.5 UNet + CLIP-L, per-GPU batch 8, 512^2 (64^2 latents), LoRA r=4, KPL on,
     18 added token vectors (2 placeholder + 16 augmentation vectors).
     precision: "fp16" = the reference driver's --mixed_precision fp16 (run_textboost_db.py:150); "fp32" = its default no-AMP mode
@@ -59,7 +59,7 @@ def build_step(batch=8, latent=64, unet_geo: UNetGeometry = models.SD15_UNET, cl
     null = frozen.forward(null_ids, pins=False).clone()
     del frozen
     te = HipTextEncoder(clip_geo, csd, batch, mode="fp32" if f32 else "autocast", lora_rank=lora_rank, n_slots=2, device=device,
-                        seed=weight_seed + 2, **({"lora_targets": lora_targets} if lora_targets is not None else {}))
+                        seed=weight_seed + 2, **({"lora_targets": lora_targets} if lora_targets is not None else {}), **({"use_dora": True} if use_dora else {}))
     del csd
     te.set_null_embedding(null)
     teacher.set_null_embedding(null)

@@ -364,7 +364,7 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
     if args.lora_rank > 64:   # (checked here, with the other options that still raise further down, before the encoder allocates for the rank)
         raise NotImplementedError(f"--lora_rank {args.lora_rank}: the text-encoder adapter kernels take ranks up to 64")
     te = HipTextEncoder(clip_geo, ctx.csd, B, mode=te_mode, lora_rank=args.lora_rank, n_slots=1, device=dev, seed=args.seed,
-                        lora_targets=getattr(args, "lora_target_modules", None))
+                        lora_targets=getattr(args, "lora_target_modules", None), use_dora=bool(getattr(args, "use_dora", False)))
     if final:
         ctx.csd = None
     te.set_null_embedding(null)
