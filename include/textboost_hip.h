@@ -341,6 +341,17 @@ int tb_chan_mix(const float* in, const float* W, const float* bias, float* out, 
  * eps = e_u + g (e_c - e_u); m0 = (x - sigma_t eps) / alpha_t; x = ca x + cb m0 + cc m_prev; m_prev = m0; x2 = fp16 (x | x) for the next call */
 int tb_dpm_step(float* x, const void* eps2, float* m_prev, void* x2, int64_t n_per_b, int B, float guidance, float alpha_t, float sigma_t,
                 float ca, float cb, float cc, tb_stream_t stream);
+/* ---- image editing (csrc/edit.hip; inference.py --init-image / --mask, textboost_amd/edit.py) ----
+ * tb_dpm_step plus the inpainting select, one launch: after the step (same arithmetic, same bits; m_prev = the unblended data prediction)
+ *   x[b, j] = mask[j % hw] ? x[b, j] : keep_a z0[j] + keep_s noise[b, j]      then x2 = fp16 (x | x)
+ * z0 fp32 [n_per_b] (the encoded photo, shared by all B), noise fp32 [B, n_per_b], mask u8 [hw] (non-zero = repaint; shared by channels and
+ * images), n_per_b % hw == 0, B <= 65535.  (keep_a, keep_s) = (alpha, sigma) of the NEXT step; with (1, 0) a kept element is z0 exactly. */
+int tb_dpm_step_blend(float* x, const void* eps2, float* m_prev, void* x2, int64_t n_per_b, int B, float guidance, float alpha_t, float sigma_t,
+                      float ca, float cb, float cc, const float* z0, const float* noise, const uint8_t* mask, int hw, float keep_a,
+                      float keep_s, tb_stream_t stream);
+/* dst[y][x] = mask[y][x] ? gen[y][x] : orig[y][x] on resident RGBX images of w x h pixels (strides in pixels), mask u8 (stride in bytes) */
+int tb_img_paste(const uint32_t* gen, int64_t gstride, const uint32_t* orig, int64_t ostride, const uint8_t* mask, int64_t mstride,
+                 uint32_t* dst, int64_t dstride, int w, int h, tb_stream_t stream);
 /* (decoded / 2 + 0.5).clamp(0, 1): NHWC fp32 [B*HW, ld >= C] -> NCHW fp32 [B, C, HW] */
 int tb_vae_image(const float* decoded, int64_t ld, float* image, int B, int HW, int C, tb_stream_t stream);
 /* the same decoder output as bytes: decoded fp32 [B*HW, ld >= 3] (R, G, B in the first three columns) -> image u32 [B*HW] in the resident RGBX

@@ -3,7 +3,7 @@
 textboost_amd/generate.py.
 
     python inference.py <output_dir> --model <diffusers model dir> --prompt "photo of a <dog> dog" [--seeds 0 1 2 3] [--output grid.jpg]
-        [--checkpoint N] [--with <output_dir> ...] [--weights W ...]
+        [--checkpoint N] [--with <output_dir> ...] [--weights W ...] [--init-image photo.jpg [--strength S] [--mask mask.png [--no-paste]]]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -23,6 +23,14 @@ word and one column per seed, and `<output stem>_attn.npz` with `maps` fp32 [see
 `<prompt>_<seed>_attn.jpg` / `.npz` pair per seed.  Without a word the placeholder tokens (of all composed runs) that occur in the prompt are taken.  The images
 themselves do not change.
 
+--init-image FILE edits a photo instead of starting from noise (textboost_amd/edit.py; diffusers' img2img pipeline and, with
+--mask, the latent blend of its inpaint pipeline for a 4-channel UNet): the photo gets a training image's geometry (short edge to the model's
+resolution with Lanczos, centre crop), is encoded once by the VAE encoder (the distribution's mode) and noised to the level --strength S in
+(0, 1] selects (default 0.8): the last int(steps * S) steps run, each seed's latent being its image's noise.  --mask FILE (the photo's size;
+white = repaint) keeps everything else: after every step the unmasked latent cells are reset to the photo's at that noise level, and the
+decoded region is pasted into the prepared photo, so pixels outside the mask are the photo's bytes (--no-paste writes the plain decode).  One
+photo and one mask serve all --seeds; --with, --weights, --checkpoint and --attn-map work as before.
+
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
 latent of a seed is drawn on the CPU (textboost_amd.generate.seeded_latent), the same on every machine."""
@@ -35,6 +43,9 @@ import sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+
+DEFAULT_STRENGTH = 0.8
 
 
 def build_parser():
@@ -54,6 +65,14 @@ def build_parser():
                    help="further trained output directories composed with `path` (subject x style)")
     p.add_argument("--weights", type=float, nargs="+", default=None, metavar="W",
                    help="adapter weight per run, `path` first (default: 1 each)")
+    p.add_argument("--init-image", dest="init_image", type=str, default=None, metavar="FILE",
+                   help="edit this photo instead of starting from noise (one photo for all --seeds)")
+    p.add_argument("--strength", type=float, default=None, metavar="S",
+                   help=f"with --init-image: how much of the schedule runs, in (0, 1] (default {DEFAULT_STRENGTH})")
+    p.add_argument("--mask", type=str, default=None, metavar="FILE",
+                   help="with --init-image: repaint only where this picture (same size as the photo) is white")
+    p.add_argument("--no-paste", dest="no_paste", action="store_true",
+                   help="with --mask: write the plain decode instead of pasting the repainted region into the photo")
     return p
 
 
@@ -95,6 +114,40 @@ def load_runs(args):
                 raise SystemExit(f"inference.py: {what} {text!r} uses {tok}, which both {first[tok]} and {dropped} hold: ambiguous (the first "
                                  "run's vector would be taken); rename the token in one run or leave it out of the prompt")
     return run
+
+
+def check_edit_args(args):
+    """--init-image / --strength / --mask: every refusal, on the host.  -> None (text-to-image) or {"rgb": uint8 [H, W, 3], "mask": PIL "L" image
+    or None, "strength": float}"""
+    from textboost_amd import edit as E
+    if args.init_image is None:
+        for flag, given in (("--mask", args.mask is not None), ("--strength", args.strength is not None)):
+            if given:
+                raise SystemExit(f"inference.py: {flag} needs --init-image FILE (the photo to edit)")
+        return None
+    strength = DEFAULT_STRENGTH if args.strength is None else args.strength
+    try:
+        E.strength_begin(args.steps, strength)
+    except ValueError as e:
+        raise SystemExit(f"inference.py: --strength: {e}")
+    try:
+        rgb = E.load_rgb(args.init_image)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"inference.py: --init-image {args.init_image}: cannot be read as a picture ({e})")
+    mask = None
+    if args.mask is not None:
+        try:
+            mask = E.load_mask(args.mask)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"inference.py: --mask {args.mask}: cannot be read as a picture ({e})")
+        if mask.size != (rgb.shape[1], rgb.shape[0]):
+            raise SystemExit(f"inference.py: --mask {args.mask} is {mask.size[0]} x {mask.size[1]}, --init-image {args.init_image} is "
+                             f"{rgb.shape[1]} x {rgb.shape[0]}: the mask must have the photo's size")
+    try:
+        E.check_vae_has_encoder(args.model)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"inference.py: --init-image: {e}")
+    return {"rgb": rgb, "mask": mask, "strength": strength}
 
 
 def attn_map_words(model_dir, run, prompt, requested):
@@ -154,6 +207,7 @@ def main(argv=None):
     words = positions = None
     if args.attn_map is not None:        # every refusal before anything reaches the device
         words, positions = attn_map_words(args.model, run, args.prompt, args.attn_map)
+    edit = check_edit_args(args)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("inference.py needs an MI355X: the product path has no CPU fallback")
@@ -172,7 +226,24 @@ def main(argv=None):
         if words is not None:
             from textboost_amd.attn_maps import AttnMapRecorder
             recorder = AttnMapRecorder(pipe.unet)
-        rgbx = pipe.images(states[1], states[0], latents, what=f"prompt {args.prompt!r}, seeds {args.seeds}", maps=recorder)
+        what = f"prompt {args.prompt!r}, seeds {args.seeds}"
+        if edit is None:
+            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder)
+        else:       # a seed's latent is the noise of its image; the photo is encoded once
+            import numpy as np
+            from textboost_amd import edit as E
+            enc = E.EditEncoder(args.model, pipe.size)
+            init_rgbx, pixels = E.prepare_image(edit["rgb"], enc.S)
+            z0 = enc.encode(pixels)
+            del enc
+            latent_mask = pixel_mask = None
+            if edit["mask"] is not None:
+                pm, lm = E.prepare_mask(edit["mask"], init_rgbx.shape[0], cell=init_rgbx.shape[0] // pipe.size)
+                latent_mask = torch.from_numpy(np.ascontiguousarray(lm)).to(pipe.dev)
+                if not args.no_paste:
+                    pixel_mask = torch.from_numpy(np.ascontiguousarray(pm)).to(pipe.dev)
+            rgbx = pipe.edit_images(states[1], states[0], latents, z0, edit["strength"], latent_mask=latent_mask, pixel_mask=pixel_mask,
+                                    init_rgbx=init_rgbx if pixel_mask is not None else None, maps=recorder, what=what)
         from PIL import Image
         images = [Image.fromarray(augment.to_host_rgb(rgbx[k])) for k in range(n)]
         word_maps = None

@@ -165,6 +165,8 @@ _SIGS = {
     "tb_vae_sample": ([_VP, _I64, _VP, _VP, _I, _I, _I, _F, _VP], C.c_int),
     "tb_chan_mix": ([_VP, _VP, _VP, _VP, _I, _I, _I, _F, _VP], C.c_int),
     "tb_dpm_step": ([_VP, _VP, _VP, _VP, _I64, _I, _F, _F, _F, _F, _F, _F, _VP], C.c_int),
+    "tb_dpm_step_blend": ([_VP, _VP, _VP, _VP, _I64, _I, _F, _F, _F, _F, _F, _F, _VP, _VP, _VP, _I, _F, _F, _VP], C.c_int),
+    "tb_img_paste": ([_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _I, _I, _VP], C.c_int),
     "tb_vae_image": ([_VP, _I64, _VP, _I, _I, _I, _VP], C.c_int),
     "tb_vae_image_rgbx": ([_VP, _I64, _VP, _I, _I, _VP], C.c_int),
     "tb_conv_to4": ([_VP, _I64, _VP, _VP, _VP, _I, _I, _I, _I, _VP], C.c_int),

@@ -2,6 +2,7 @@
 // losses, GEGLU backward, nearest-upsample backward, residual adds, timestep embedding.
 // Reference call sites are cited per kernel (all in /root/reference/train_textboost.py unless noted).
 #include "common.h"
+#include "dpm_step.h"
 #include "../../include/textboost_hip.h"
 
 namespace {
@@ -596,11 +597,8 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(float* __restrict__ x, co
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t tot = n_per_b * B;
   if (i >= tot) return;
-  const float eu = (float)e[i], ec = (float)e[tot + i];
-  const float eps = eu + g * (ec - eu);
-  const float xv = x[i];
-  const float m0 = (xv - sigma_t * eps) / alpha_t;
-  const float xn = ca * xv + cb * m0 + cc * m_prev[i];
+  float m0, xn;
+  dpm_update((float)e[i], (float)e[tot + i], x[i], m_prev[i], g, alpha_t, sigma_t, ca, cb, cc, m0, xn);   // dpm_step.h: shared with edit.hip
   m_prev[i] = m0;
   x[i] = xn;
   x2[i] = (f16)xn;

@@ -6,6 +6,7 @@ eval_dreambooth.py (`load_pipeline` :175-215, `generate_from_pipeline` :218-267,
     load_text_encoder(model_dir, run, ...)      -> HipTextEncoder (+ tokenizer) with the adapter, the learned rows and the null-embedding pins
     Pipeline.from_model_dir(model_dir, ...)     -> UNet, VAE decoder and sampler executors, built once per run
     Pipeline.set_unet_adapters([...])           -> attn2.to_k / to_v = W + sum w_i B_i A_i (one exact-fp32 GEMM, rounded once); [] = the base weights
+    Pipeline.edit_images(cond, uncond, noise, z0, strength, ...)  -> `images` from an encoded photo, optionally inside a mask (edit.py)
     generate_instance(pipe, base, run, ...)     -> <outdir>/seed<s>/<instance>/<prompt>.png for every seed, 25 prompts each
 
 Device work: `HipTextEncoder.forward`, `HipSampler.denoise` (guided DPM-Solver++ steps on `HipUNet.forward`), `HipVAEDecoder.decode_rgbx`
@@ -414,6 +415,26 @@ class Pipeline:
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         return self.vae.decode_rgbx(x)
+
+    def edit_images(self, cond, uncond, noise, z0, strength, latent_mask=None, pixel_mask=None, init_rgbx=None, maps=None,
+                    what: str = "") -> torch.Tensor:
+        """`images` from an encoded photo (textboost_amd/edit.py; `HipSampler.denoise_from`): noise fp32 [B, 4, size, size] (a seed's latent is
+        its image's noise), z0 fp32 [1, 4, size, size] shared by the B images, latent_mask uint8 [size, size] or None (non-zero = repaint).
+        With pixel_mask (uint8 [8 size, 8 size]) and init_rgbx (the prepared photo, int32 RGBX [8 size, 8 size]) the decoded region is pasted
+        into the photo: pixels outside the mask are the photo's bytes.  -> int32 RGBX [B, 8 size, 8 size] (resident)."""
+        from . import ops
+        if (pixel_mask is None) != (init_rgbx is None):
+            raise ValueError("the paste needs both pixel_mask and init_rgbx")
+        x = self.sampler.denoise_from(cond, uncond, z0, noise, strength, mask=latent_mask, maps=maps)
+        if not bool(torch.isfinite(x).all()):
+            raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
+        rgbx = self.vae.decode_rgbx(x)
+        if pixel_mask is None:
+            return rgbx
+        out = torch.empty_like(rgbx)
+        for b in range(rgbx.shape[0]):      # one launch per image
+            ops.img_paste(rgbx[b], init_rgbx, pixel_mask, out=out[b])
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ the protocol

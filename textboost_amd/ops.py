@@ -549,6 +549,31 @@ def dpm_step(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sigma_t, ca, cb
                                 L.stream()), "tb_dpm_step")
 
 
+def dpm_step_blend(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sigma_t, ca, cb, cc, z0, noise, mask, keep_a, keep_s):
+    """`dpm_step` plus the inpainting select in the same launch (csrc/edit.hip): x = mask ? x_step : keep_a z0 + keep_s noise.
+    z0 fp32 [n_per_b] (shared by the B images), noise fp32 [B, n_per_b], mask uint8 [hw] (non-zero = repaint; shared by channels and images)."""
+    hw = mask.numel()
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (x, m_prev, z0, noise)) and mask.dtype == torch.uint8 and mask.is_contiguous()
+    assert eps2.dtype == L.half_dtype() and x2.dtype == L.half_dtype() and eps2.is_contiguous() and x2.is_contiguous()
+    assert x.numel() == B * n_per_b and m_prev.numel() == B * n_per_b and noise.numel() == B * n_per_b and z0.numel() == n_per_b
+    assert eps2.numel() == 2 * B * n_per_b and x2.numel() == 2 * B * n_per_b
+    L.check(L.lib().tb_dpm_step_blend(L.ptr(x), L.ptr(eps2), L.ptr(m_prev), L.ptr(x2), n_per_b, B, guidance, alpha_t, sigma_t, ca, cb, cc,
+                                      L.ptr(z0), L.ptr(noise), L.ptr(mask), hw, keep_a, keep_s, L.stream()), "tb_dpm_step_blend")
+
+
+def img_paste(gen, orig, mask, out=None):
+    """mask ? gen : orig per pixel: gen / orig int32 RGBX [H, W] (rows may be strided), mask uint8 [H, W] (non-zero = gen) -> int32 [H, W]"""
+    h, w = gen.shape
+    assert gen.dtype == torch.int32 and orig.dtype == torch.int32 and mask.dtype == torch.uint8
+    assert tuple(orig.shape) == (h, w) and tuple(mask.shape) == (h, w) and gen.stride(1) == 1 and orig.stride(1) == 1 and mask.stride(1) == 1
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.int32, device=gen.device)
+    assert out.dtype == torch.int32 and tuple(out.shape) == (h, w) and out.stride(1) == 1
+    L.check(L.lib().tb_img_paste(L.ptr(gen), gen.stride(0), L.ptr(orig), orig.stride(0), L.ptr(mask), mask.stride(0), L.ptr(out), out.stride(0),
+                                 w, h, L.stream()), "tb_img_paste")
+    return out
+
+
 def vae_image(decoded, image, B, HW, C):
     L.check(L.lib().tb_vae_image(L.ptr(decoded), decoded.stride(0), L.ptr(image), B, HW, C, L.stream()), "tb_vae_image")
 

@@ -8,6 +8,9 @@ SURVEY.md 8(f) row 2.
 The UNet forward, the text encoder and the VAE decoder are the executors of this package; the per-step scalar coefficients of the solver
 are host arithmetic (`DPMSolverPP2M`, float64, computed once per schedule), the update itself is one elementwise kernel (`tb_dpm_step`).
 Nothing here synchronises with the host, so the whole loop can be captured in a HIP graph.
+
+`HipSampler.denoise_from` is the same loop started mid-schedule from the latents of an encoded photo (image editing, edit.py): with a mask the
+update and the per-step select of the kept cells are one launch as well (`tb_dpm_step_blend`), so editing launches what text-to-image does.
 """
 from __future__ import annotations
 
@@ -80,8 +83,13 @@ class DPMSolverPP2M:
         a_t, s_t = self.alpha_sigma(self.sigmas[i])
         return (a_t, s_t) if self.prediction_type == "epsilon" else (1.0 / a_t, s_t / a_t)
 
-    def coefficients(self, i: int) -> Tuple[float, float, float]:
-        """x_next = ca x + cb m0 + cc m_prev  for step i  (m = data prediction)."""
+    def noise_scalars(self, i: int) -> Tuple[float, float]:
+        """(alpha, sigma) of `add_noise` at the start of step i: x_i = alpha z0 + sigma noise.  i = len(timesteps) (past the last step): (1, 0)."""
+        return self.alpha_sigma(self.sigmas[i])
+
+    def coefficients(self, i: int, begin: int = 0) -> Tuple[float, float, float]:
+        """x_next = ca x + cb m0 + cc m_prev  for step i  (m = data prediction).  begin: the first step that runs (image editing starts
+        mid-schedule, `HipSampler.denoise_from`): it has no model-output history and is first order, as step 0 is."""
         a0, st0 = self.alpha_sigma(self.sigmas[i])
         a1, st1 = self.alpha_sigma(self.sigmas[i + 1])
         if i == len(self.timesteps) - 1:      # sigma_next = 0: exp(-h) = 0, alpha_next = 1
@@ -90,7 +98,7 @@ class DPMSolverPP2M:
         h = lam1 - lam0
         e = math.expm1(-h)
         ca = st1 / st0
-        if i == 0:
+        if i == begin:
             return ca, -a1 * e, 0.0
         ap, stp = self.alpha_sigma(self.sigmas[i - 1])
         r0 = (lam0 - math.log(ap / stp)) / h
@@ -197,6 +205,48 @@ class HipSampler:
                 else:
                     self.m_prev.normal_(generator=self.generator)
             ops.dpm_step(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc)
+        return self.x
+
+    def denoise_from(self, cond_ehs, uncond_ehs, z0, noise, strength, mask=None, maps=None):
+        """Image editing: diffusers' StableDiffusionImg2ImgPipeline and, with a mask, the latent blend of StableDiffusionInpaintPipeline for a
+        4-channel UNet [3P restated: diffusers 0.29 is not installed here].  z0: the encoded image, fp32 [4, h, w] or [1, 4, h, w], shared by the B
+        rows; noise: fp32 [B, 4, h, w], the noise of each row's image.  Steps begin .. steps-1 run, begin = `edit.strength_begin(steps, strength)`,
+        from x = alpha_begin z0 + sigma_begin noise (also at strength 1, where diffusers' inpaint pipeline starts from pure noise); step
+        `begin` is first order, as step 0 of `denoise` is.  mask: uint8 [h, w] on the device (non-zero = repaint), shared by channels and rows:
+        after step i, x = mask ? x : alpha_{i+1} z0 + sigma_{i+1} noise in the step's own launch (`tb_dpm_step_blend`), so the kept cells end
+        as z0 exactly.  Nothing of one call is kept for the next: the scheduler holds no step state, `begin` is an argument.
+        Returns the final latents fp32 [B, 4, h, w]."""
+        from .edit import strength_begin
+        B, sch = self.B, self.sch
+        if not isinstance(sch, DPMSolverPP2M):
+            raise NotImplementedError(f"image editing runs on the DPM-Solver++ scheduler only, not on {type(sch).__name__}")
+        begin = strength_begin(self.steps, strength)
+        z0 = z0.reshape(self.x.shape[1:]).to(self.x.device, torch.float32).contiguous()
+        noise = noise.to(self.x.device, torch.float32).contiguous()
+        if tuple(noise.shape) != tuple(self.x.shape):
+            raise ValueError(f"noise {tuple(noise.shape)}: the sampler is built for {tuple(self.x.shape)}")
+        if mask is not None:
+            mask = mask.to(self.x.device).contiguous()
+            if mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(self.x.shape[2:]):
+                raise ValueError(f"mask {mask.dtype} {tuple(mask.shape)}: expected uint8 {tuple(self.x.shape[2:])}")
+        if maps is not None:
+            maps.zero()
+        a_b, s_b = sch.noise_scalars(begin)
+        self.x.copy_(a_b * z0 + s_b * noise)
+        self.m_prev.zero_()
+        self.x2[:B].copy_(self.x)
+        self.x2[B:].copy_(self.x)
+        ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
+        n = self.x[0].numel()
+        for i in range(begin, self.steps):
+            eps2 = self._unet_forward(i, ehs, maps)
+            a_t, s_t = sch.data_prediction_scalars(i)
+            ca, cb, cc = sch.coefficients(i, begin)
+            if mask is None:
+                ops.dpm_step(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc)
+            else:
+                k_a, k_s = sch.noise_scalars(i + 1)
+                ops.dpm_step_blend(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc, z0, noise, mask, k_a, k_s)
         return self.x
 
     def _unet_forward(self, i, ehs, maps):
