@@ -575,6 +575,24 @@ int tb_img_to_pixels(const uint32_t* src, int64_t sstride, int sw, int sh, int x
 int tb_img_pack_rgb(const uint8_t* rgb, uint32_t* dst, int64_t n_pixels, tb_stream_t stream);
 int tb_img_unpack_rgb(const uint32_t* src, int64_t sstride, int w, int h, uint8_t* rgb, tb_stream_t stream);
 
+/* ---- masked denoising loss (csrc/masked_loss.hip; --instance_mask_dir) ----------------------------------------------
+ * tb_img_to_loss_weight: crop [y0, y0 + cell * out_h) x [x0, x0 + cell * out_w) of a grey RGBX mask image (R = G = B = mask byte) -> the
+ * cell x cell box mean of the R byte as fp32 [out_h, out_w].  With S the integer byte sum of a box, every operation rounded to fp32 and no
+ * contraction: m = (float)S / (float)(255 * cell * cell), w = floor + (1 - floor) * m (bit-exact with the numpy float32 restatement).
+ * 1 <= cell <= 64, 0 <= floor < 1; a crop that leaves the sw x sh image returns -22. */
+int tb_img_to_loss_weight(const uint32_t* src, int64_t sstride, int sw, int sh, int x0, int y0, int out_h, int out_w, int cell, float floor_w,
+                          float* dst, tb_stream_t stream);
+/* tb_mse_loss_weighted: pred TB_F16 [B, C, h, w] (tb_mse_loss_weighted_f32: fp32), target fp32, weight fp32 [B, 1, h, w] >= 0.
+ *   W_b = sum_{y,x} w_b;  loss_out[0] = (1/B) sum_b [ sum_{c,y,x} w_b (pred - target)^2 / (C max(W_b, 1)) ]
+ *   dpred[b,c,y,x] = loss_scale[0] * 2 w_b[y,x] (pred - target) / (B C max(W_b, 1))   (fp32, overwritten by every launch)
+ * All-ones weights give tb_mse_loss's loss and gradient.  Two launches, a fixed-order two-stage reduction without atomics: replays are
+ * bit-identical.  ws: tb_mse_loss_weighted_workspace_bytes(B, C, h, w) bytes from the caller; loss_scale may be NULL (= 1). */
+int64_t tb_mse_loss_weighted_workspace_bytes(int B, int C, int h, int w);
+int tb_mse_loss_weighted(const void* pred, const float* target, const float* weight, float* dpred, float* loss_out, const float* loss_scale,
+                         int B, int C, int h, int w, float* ws, int64_t ws_bytes, tb_stream_t stream);
+int tb_mse_loss_weighted_f32(const float* pred, const float* target, const float* weight, float* dpred, float* loss_out,
+                             const float* loss_scale, int B, int C, int h, int w, float* ws, int64_t ws_bytes, tb_stream_t stream);
+
 /* ---- CLIP ViT patch embedding (csrc/clip_vision.hip; the image tower of the CLIP-T / CLIP-I evaluation, textboost_amd/clip_score.py) -------
  * img: B resident RGBX images of S x S pixels, image b at img + b * img_stride, rows row_stride pixels apart.  P = (S / patch)^2 patches.
  * w: TB_F16 [D][ldw], K = 4 patch^2 columns in the order (ky, kx, R G B X) then zeros up to Kp (a multiple of 32): the conv weight with

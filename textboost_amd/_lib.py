@@ -232,7 +232,11 @@ _SIGS = {
     "tb_img_to_pixels": ([_VP, _I64, _I, _I, _I, _I, _VP, _I, _VP], C.c_int),
     "tb_img_pack_rgb": ([_VP, _VP, _I64, _VP], C.c_int),
     "tb_img_unpack_rgb": ([_VP, _I64, _I, _I, _VP, _VP], C.c_int),
-    "tb_clip_patch_embed": ([_VP, _I64, _I64, _I, _I, _I, _VP, _I64, _I, _VP, _VP, _VP, _VP, _I64, _I, _VP], C.c_int),
+    "tb_img_to_loss_weight": ([_VP, _I64, _I, _I, _I, _I, _I, _I, _I, _F, _VP, _VP], C.c_int),
+    "tb_mse_loss_weighted_workspace_bytes": ([_I, _I, _I, _I], _I64),
+    "tb_mse_loss_weighted": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _I64, _VP], C.c_int),
+    "tb_mse_loss_weighted_f32": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _I64, _VP], C.c_int),
+    "tb_clip_patch_embed":([_VP, _I64, _I64, _I, _I, _I, _VP, _I64, _I, _VP, _VP, _VP, _VP, _I64, _I, _VP], C.c_int),
     "tb_rmsnorm_fwd": ([_VP, _I64, _VP, _I64, _I, _VP, _I64, _I, _F, _VP], C.c_int),
     "tb_attention_rel_fwd": ([C.POINTER(AttnDesc), _VP, _VP, _VP], C.c_int),
     "tb_gated_gelu_tanh": ([_VP, _I64, _VP, _I64, _I64, _I, _VP], C.c_int),

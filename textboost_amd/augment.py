@@ -13,6 +13,9 @@ Pillow.  The host only draws the random parameters (np.random / random / torch, 
 and builds O(W + H) index / coefficient tables.  There is no CPU fallback: a missing library raises.
 
 An image is an int32 CUDA tensor [H, W] (one RGBX pixel per element).
+
+A subject mask (--instance_mask_dir) is such an image with R = G = B = the mask byte (`to_device_mask`): it rides
+through the same kernels as the image's `companion`, with the image's drawn parameters, and draws nothing itself.
 """
 from __future__ import annotations
 
@@ -51,6 +54,15 @@ def to_device_image(rgb) -> torch.Tensor:
     return ops.img_pack_rgb(t.cuda().contiguous())
 
 
+def to_device_mask(mask) -> torch.Tensor:
+    """uint8 [H, W] (Pillow "L": white = subject) -> resident grey RGBX image (R = G = B = mask byte), the form in which a mask rides through
+    the image kernels unchanged: they zero X and treat R, G and B alike."""
+    t = torch.from_numpy(np.array(mask, copy=True)) if isinstance(mask, np.ndarray) else torch.as_tensor(mask)
+    if t.dtype != torch.uint8 or t.dim() != 2:
+        raise ValueError("expected a uint8 [H, W] mask")
+    return ops.img_pack_rgb(t.cuda()[:, :, None].expand(-1, -1, 3).contiguous())
+
+
 def to_host_rgb(img: torch.Tensor) -> np.ndarray:
     return ops.img_unpack_rgb(img).cpu().numpy()
 
@@ -78,6 +90,20 @@ def resize(img: torch.Tensor, size_wh: Tuple[int, int], filt: int) -> torch.Tens
 
 def _gather(img, xt: np.ndarray, yt: np.ndarray, gray=False):
     return ops.img_gather(img, _dev_table(xt, img.device), _dev_table(yt, img.device), gray)
+
+
+def _gather_pair(img, companion, xt: np.ndarray, yt: np.ndarray):
+    """`_gather` on the image and, through the same device tables, on its companion (the subject mask of --instance_mask_dir: a grey RGBX image
+    of the image's shape that every geometric op replays with the image's drawn parameters).  companion None: exactly `_gather`."""
+    if companion is None:
+        return _gather(img, xt, yt), None
+    dx, dy = _dev_table(xt, img.device), _dev_table(yt, img.device)
+    return ops.img_gather(img, dx, dy, False), ops.img_gather(companion, dx, dy, False)
+
+
+def _ret(image, prompt, companion):
+    """the ops return (image, prompt), and (image, prompt, companion) when they were handed a companion"""
+    return (image, prompt) if companion is None else (image, prompt, companion)
 
 
 def _center_crop_offsets(W: int, H: int, crop_h: int, crop_w: int):
@@ -121,7 +147,7 @@ def _compute_padding(h, w, scale):
     return round(((h / scale) - h) / 2), round(((w / scale) - w) / 2)
 
 
-def adjust_scale(image, prompt, inversion=False):
+def adjust_scale(image, prompt, inversion=False, companion=None):
     """paired_augmentation.py:20-49 -- pad(edge) + affine(scale, BICUBIC) + center_crop in ONE launch."""
     scale_factor = np.random.uniform(0.34, 1.4)
     H, W = image.shape
@@ -133,6 +159,8 @@ def adjust_scale(image, prompt, inversion=False):
     crop_h, crop_w = h, w  # center_crop(image, (h, w))
     ox, oy = _center_crop_offsets(PW, PH, crop_h, crop_w)
     image = ops.img_affine_bicubic(image, m, px, py, ox, oy, crop_w, crop_h)
+    if companion is not None:
+        companion = ops.img_affine_bicubic(companion, m, px, py, ox, oy, crop_w, crop_h)
     if inversion:
         add = "<zoom-out_0> <zoom-out_1>" if scale_factor < 0.6 else "<zoom-in_0> <zoom-in_1>" if scale_factor > 1.2 else ""
     else:
@@ -142,22 +170,22 @@ def adjust_scale(image, prompt, inversion=False):
             add = np.random.choice(["zoomed in ", "close up "])
         else:
             add = ""
-    return image, add + prompt
+    return _ret(image, add + prompt, companion)
 
 
-def horizontal_flip(image, prompt, inversion=False):
+def horizontal_flip(image, prompt, inversion=False, companion=None):
     """paired_augmentation.py:79-92."""
     H, W = image.shape
-    image = _gather(image, np.arange(W - 1, -1, -1), np.arange(H))
+    image, companion = _gather_pair(image, companion, np.arange(W - 1, -1, -1), np.arange(H))
     word = "<hflip>" if inversion else "horizontally flipped"
     if np.random.rand() < 0.5:
         prompt = word + " " + prompt
     else:
         prompt = prompt + ", " + word
-    return image, prompt
+    return _ret(image, prompt, companion)
 
 
-def horizontal_translate(image, prompt, inversion=False):
+def horizontal_translate(image, prompt, inversion=False, companion=None):
     """paired_augmentation.py:95-134 -- pad(edge) + affine(translate, NEAREST) + center_crop composed into one index map, one launch."""
     shift_dir = np.random.randint(0, 2)
     H, W = image.shape
@@ -179,17 +207,19 @@ def horizontal_translate(image, prompt, inversion=False):
     fx = np.where(cx >= 0, ax[np.maximum(cx, 0)], -1)
     fy = np.where(cy >= 0, ay[np.maximum(cy, 0)], -1)
     fx = np.where(fx >= 0, pad_x[np.maximum(fx, 0)], -1)
-    return _gather(image, fx, fy), prompt
+    image, companion = _gather_pair(image, companion, fx, fy)
+    return _ret(image, prompt, companion)
 
 
-def grayscale(image, prompt, inversion=False, size=None):
-    """paired_augmentation.py:163-174."""
+def grayscale(image, prompt, inversion=False, size=None, companion=None):
+    """paired_augmentation.py:163-174.  A companion mask passes through untouched: the luma of a grey pixel is the pixel itself
+    (19595 + 38470 + 7471 = 65536), so skipping the launch changes no byte."""
     H, W = image.shape
     image = _gather(image, np.arange(W), np.arange(H), gray=True)
-    return image, f"{prompt}, " + ("<grayscale_0> <grayscale_1>" if inversion else "grayscale")
+    return _ret(image, f"{prompt}, " + ("<grayscale_0> <grayscale_1>" if inversion else "grayscale"), companion)
 
 
-def random_resized_crop(image, target_size, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.)):
+def random_resized_crop(image, target_size, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), companion=None):
     """paired_augmentation.py:177-217 (`random` module draws); the crop is a strided view, only the BICUBIC resize touches memory."""
     height, width = image.shape
     area = width * height * random.uniform(*scale)
@@ -198,22 +228,28 @@ def random_resized_crop(image, target_size, scale=(0.08, 1.0), ratio=(3. / 4., 4
     new_height = min(int(round(math.sqrt(area / aspect_ratio))), height)
     x = random.randint(0, width - new_width)
     y = random.randint(0, height - new_height)
-    return resize(image[y:y + new_height, x:x + new_width], target_size, BICUBIC)
+    out = resize(image[y:y + new_height, x:x + new_width], target_size, BICUBIC)
+    if companion is None:
+        return out
+    return out, resize(companion[y:y + new_height, x:x + new_width], target_size, BICUBIC)
 
 
-def crop(image, prompt, inversion=False):
+def crop(image, prompt, inversion=False, companion=None):
     """paired_augmentation.py:220-233."""
     H, W = image.shape
-    image = random_resized_crop(image, (W, H), ratio=(1.0, 1.0))
+    if companion is None:
+        image = random_resized_crop(image, (W, H), ratio=(1.0, 1.0))
+    else:
+        image, companion = random_resized_crop(image, (W, H), ratio=(1.0, 1.0), companion=companion)
     add = "<crop>" if inversion else "cropped"
     if np.random.random() < 0.5:
         prompt = f"{add} {prompt}"
     else:
         prompt = f"{prompt}, {add}"
-    return image, prompt
+    return _ret(image, prompt, companion)
 
 
-def square_photo_collage(image, prompt, inversion=False):
+def square_photo_collage(image, prompt, inversion=False, companion=None):
     """paired_augmentation.py:253-277: BICUBIC resize to one cell, black 1-pixel frame, axis x axis tiling (frame + tiling = one index map)."""
     axis = np.random.randint(2, 4)
     H, W = image.shape
@@ -223,13 +259,18 @@ def square_photo_collage(image, prompt, inversion=False):
     xs, ys = np.arange(sw), np.arange(sh)
     xs[[0, -1]] = -1
     ys[[0, -1]] = -1
-    image = _gather(small, np.tile(xs, axis), np.tile(ys, axis))
+    small_c = None if companion is None else resize(companion, (grid_h, grid_w), BICUBIC)
+    image, companion = _gather_pair(small, small_c, np.tile(xs, axis), np.tile(ys, axis))
     prompt = ("<collage_0> <collage_1> " if inversion else "photo collage of ") + prompt
-    return image, prompt
+    return _ret(image, prompt, companion)
 
 
 class PairedAugmentation:
-    """paired_augmentation.py:280-351: same constructor, same gates and op choice (np.random), returns (image, prompt, None)."""
+    """paired_augmentation.py:280-351: same constructor, same gates and op choice (np.random), returns (image, prompt, mask).
+
+    `mask` (optional) is a resident grey RGBX image of the image's shape: the subject mask of --instance_mask_dir.  It goes through the same
+    geometric ops, collage and hflip as the image, with the image's drawn parameters and the same kernels; the colour op skips it (the
+    identity on grey).  It draws nothing: a call with a mask consumes the same np.random / random / torch sequence as one without."""
 
     def __init__(self, hflip="false", inversion=False, p=0.5, color_prob=0.2, augment_prompt=True, ops="object"):
         assert hflip.lower() in ("true", "false", "inversion"), f"Invalid hflip value: {hflip}"
@@ -251,19 +292,25 @@ class PairedAugmentation:
         elif hflip == "true":
             self.hflip = True
 
-    def __call__(self, image, prompt):
+    def __call__(self, image, prompt, mask=None):
         if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.int32 and image.dim() == 2):
             raise TypeError("PairedAugmentation takes a resident RGBX image (int32 CUDA tensor [H, W]); see to_device_image()")
+        if mask is not None and not (isinstance(mask, torch.Tensor) and mask.device == image.device and mask.dtype == torch.int32
+                                     and mask.shape == image.shape):
+            raise TypeError("the mask is a resident grey RGBX image of the image's shape; see to_device_mask()")
         if self.hflip and np.random.rand() < 0.5:
             H, W = image.shape
-            image = _gather(image, np.arange(W - 1, -1, -1), np.arange(H))
+            image, mask = _gather_pair(image, mask, np.arange(W - 1, -1, -1), np.arange(H))
         for op_list, prob in ((self.geometric_ops, self.p), (self.other_ops, self.p), (self.color_ops, self.color_prob)):
             if len(op_list) > 0 and np.random.rand() < prob:
                 op = np.random.choice(op_list)
-                image, new_prompt = op(image, prompt, self.inversion)
+                if mask is None:
+                    image, new_prompt = op(image, prompt, self.inversion)
+                else:
+                    image, new_prompt, mask = op(image, prompt, self.inversion, companion=mask)
                 if self.augment_prompt:
                     prompt = new_prompt
-        return image, prompt, None
+        return image, prompt, mask
 
 
 # ------------------------------------------------------------------------------------------------------------------ the feeder
@@ -300,14 +347,33 @@ class PromptFeeder:
 class DeviceFeeder:
     """`TextBoostDataset.__getitem__` + `collate_fn` (dataset.py:353-381, :420-457) for the instance images, on the device.
 
-    images: list of (resident RGBX image, instance_token).  `batch(indices)` returns {"input_ids": int64 [B, 77] (CPU, as the reference's
-    collate_fn), "pixel_values": fp32 [B, 3, size, size] on the device, "prompts": list[str]}."""
+    images: list of (resident RGBX image, instance_token) or (image, instance_token, mask), mask a resident grey RGBX image of the image's
+    shape (`to_device_mask`) or None.  `batch(indices)` returns {"input_ids": int64 [B, 77] (CPU, as the reference's collate_fn),
+    "pixel_values": fp32 [B, 3, size, size] on the device, "prompts": list[str]} and, when any image carries a mask, "loss_weight": fp32
+    [B, 1, size / 8, size / 8]: the mask after the image's augmentation, Lanczos resize and crop, box-averaged over the VAE's 8 x 8 cells,
+    w = mask_floor + (1 - mask_floor) * mean / 255.  An image without a mask in such a run gets an all-white one (it trains unmasked).  The
+    mask draws nothing: pixel_values, prompts and the random streams are those of the same feeder without masks."""
 
-    def __init__(self, images: Sequence[Tuple[torch.Tensor, str]], tokenizer, templates: Sequence[str], size=512, center_crop=False,
-                 augment_pipe: Optional[PairedAugmentation] = None):
+    LATENT_CELL = 8   # pixels per latent cell of every supported VAE
+
+    def __init__(self, images: Sequence[tuple], tokenizer, templates: Sequence[str], size=512, center_crop=False,
+                 augment_pipe: Optional[PairedAugmentation] = None, mask_floor: float = 0.0):
         if len(images) == 0:
             raise ValueError("no instance images")
-        self.images = list(images)
+        if not 0.0 <= mask_floor < 1.0:
+            raise ValueError(f"mask_floor {mask_floor}: 0 <= F < 1")
+        items = [tuple(it) + (None,) * (3 - len(it)) for it in images]
+        self.has_mask = any(m is not None for _, _, m in items)
+        if self.has_mask:
+            if size % self.LATENT_CELL:
+                raise ValueError(f"the masked loss needs a resolution that is a multiple of {self.LATENT_CELL}, not {size}")
+            items = [(im, tok, m if m is not None else torch.full_like(im, 0x00FFFFFF)) for im, tok, m in items]
+            for im, _, m in items:
+                if m.shape != im.shape or m.dtype != torch.int32 or m.device != im.device:
+                    raise ValueError("a mask is a resident grey RGBX image of its image's shape (to_device_mask)")
+        self.images = [(im, tok) for im, tok, _ in items]
+        self.masks = [m for _, _, m in items] if self.has_mask else None
+        self.mask_floor = float(mask_floor)
         self.templates = list(templates)
         self.size = size
         self.center_crop = center_crop
@@ -317,14 +383,20 @@ class DeviceFeeder:
     def __len__(self):
         return len(self.images)
 
-    def item_into(self, index: int, dst: torch.Tensor):
-        """One sample; pixel_values written into dst [3, size, size].  Returns (input_ids [1, 77], prompt)."""
+    def item_into(self, index: int, dst: torch.Tensor, weight_dst: Optional[torch.Tensor] = None):
+        """One sample; pixel_values written into dst [3, size, size] and, with masks, the loss weights into weight_dst [1, size/8, size/8].
+        Returns (input_ids [1, 77], prompt)."""
         image, instance_token = self.images[index % len(self.images)]
+        mask = self.masks[index % len(self.images)] if self.has_mask else None
+        if self.has_mask and weight_dst is None:
+            raise ValueError("this feeder carries masks: item_into needs weight_dst")
         prompt_idx = random.randint(0, len(self.templates) - 1)
         prompt = self.templates[prompt_idx].format(instance_token)
         if self.augment_pipe is not None:
-            image, prompt, _ = self.augment_pipe(image, prompt)
+            image, prompt, mask = self.augment_pipe(image, prompt, mask)
         image = resize_short_edge(image, self.size, LANCZOS)
+        if mask is not None:
+            mask = resize_short_edge(mask, self.size, LANCZOS)
         H, W = image.shape
         if self.center_crop:
             y1 = max(0, int(round((H - self.size) / 2.0)))
@@ -335,18 +407,26 @@ class DeviceFeeder:
             y1 = int(torch.randint(0, H - self.size + 1, size=(1,)).item())
             x1 = int(torch.randint(0, W - self.size + 1, size=(1,)).item())
         ops.img_to_pixels(image, x1, y1, dst)
+        if mask is not None:
+            ops.img_to_loss_weight(mask, x1, y1, weight_dst, cell=self.LATENT_CELL, floor=self.mask_floor)
         return self.tokenize(prompt), prompt
 
-    def batch(self, indices: Sequence[int], out: Optional[torch.Tensor] = None):
+    def batch(self, indices: Sequence[int], out: Optional[torch.Tensor] = None, weight_out: Optional[torch.Tensor] = None):
         B = len(indices)
+        dev = self.images[0][0].device
         if out is None:
-            out = torch.empty(B, 3, self.size, self.size, dtype=torch.float32, device=self.images[0][0].device)
+            out = torch.empty(B, 3, self.size, self.size, dtype=torch.float32, device=dev)
+        if self.has_mask and weight_out is None:
+            weight_out = torch.empty(B, 1, self.size // self.LATENT_CELL, self.size // self.LATENT_CELL, dtype=torch.float32, device=dev)
         ids, prompts = [], []
         for b, i in enumerate(indices):
-            t, p = self.item_into(i, out[b])
+            t, p = self.item_into(i, out[b], weight_out[b] if self.has_mask else None)
             ids.append(t)
             prompts.append(p)
-        return {"input_ids": torch.cat(ids, dim=0), "pixel_values": out, "prompts": prompts}
+        res = {"input_ids": torch.cat(ids, dim=0), "pixel_values": out, "prompts": prompts}
+        if self.has_mask:
+            res["loss_weight"] = weight_out
+        return res
 
 
 class PrefetchFeeder:
@@ -355,9 +435,14 @@ class PrefetchFeeder:
     behind the running step.  Here batch k+1 is produced on a side stream into a staging buffer while step k runs; `commit()` makes the step's
     stream wait for it and copies pixels / ids into the step's static inputs (one device-to-device copy)."""
 
-    def __init__(self, feeder: DeviceFeeder, batch: int, pixel_values: torch.Tensor, input_ids: torch.Tensor):
+    def __init__(self, feeder: DeviceFeeder, batch: int, pixel_values: torch.Tensor, input_ids: torch.Tensor,
+                 loss_weight: Optional[torch.Tensor] = None):
         self.feeder, self.batch = feeder, batch
         self.pixel_values, self.input_ids = pixel_values, input_ids
+        if (loss_weight is not None) != bool(getattr(feeder, "has_mask", False)):
+            raise ValueError("a feeder with masks needs the step's loss_weight input, and one without must not be given it")
+        self.loss_weight = loss_weight   # the masked loss's static input (TextBoostStep.enable_loss_weight), staged beside the pixels
+        self.weight_staging = torch.empty_like(loss_weight) if loss_weight is not None else None
         self.staging = torch.empty_like(pixel_values)
         self.ids_staging = torch.empty_like(input_ids)
         self.side = torch.cuda.Stream(device=pixel_values.device)
@@ -369,7 +454,10 @@ class PrefetchFeeder:
         if self.consumed is not None:
             self.side.wait_event(self.consumed)  # NOT wait_stream(main): that would put the side stream (and the host's uploads) behind the step
         with torch.cuda.stream(self.side):
-            b = self.feeder.batch(indices, out=self.staging)
+            if self.loss_weight is None:   # (the call of a run without masks is what it was)
+                b = self.feeder.batch(indices, out=self.staging)
+            else:
+                b = self.feeder.batch(indices, out=self.staging, weight_out=self.weight_staging)
             self.ids_staging.copy_(b["input_ids"], non_blocking=True)
             self.ready.record(self.side)
         self.pending = b
@@ -381,6 +469,8 @@ class PrefetchFeeder:
         torch.cuda.current_stream().wait_event(self.ready)
         self.pixel_values.copy_(self.staging)
         self.input_ids.copy_(self.ids_staging)
+        if self.loss_weight is not None:
+            self.loss_weight.copy_(self.weight_staging)
         self.consumed = torch.cuda.Event()
         self.consumed.record(torch.cuda.current_stream())
         b, self.pending = self.pending, None

@@ -90,6 +90,16 @@ EXTENSION_FLAGS = [
     # its target_modules line (train_textboost.py:706)
     ("--lora_target_modules", dict(type="str", nargs="+", default=["q_proj", "k_proj", "v_proj"], choices=LORA_TARGET_CHOICES, metavar="M")),
 ]
+# masked training loss (also not the reference's: it has the slot -- its step's `mask` branch, :1086-1088 -- and nothing that
+# fills it).  A list of its own, like the adapter's variants: EXTENSION_FLAGS stays the one-entry list tests/test_lora_targets_host.py pins
+MASKED_LOSS_FLAGS = [
+    ("--instance_mask_dir", dict(type="str", default=None, help=(
+        "directory of subject masks: instance image <stem>.<ext> needs <stem>.<any supported image extension> there, read as Pillow 'L' and of "
+        "the image's pixel size.  White is the subject (loss weight 1), black the background.  The bytes are used as they are: soft masks are "
+        "allowed and there is NO threshold (unlike inference.py --mask).  --concepts_list entries may carry the key instance_mask_dir instead."))),
+    ("--mask_floor", dict(type="float", default=0.0, help=(
+        "loss weight F of a background pixel, 0 <= F < 1: w = F + (1 - F) * mask.  Needs --instance_mask_dir; does not apply to loss_weight.pt"))),
+]
 # the adapter's variants (also not the reference's).  --use_dora: peft's LoraConfig(use_dora=True) -- every adapted Linear also trains a magnitude
 # per output row; needs --lora_rank > 0
 ADAPTER_VARIANT_FLAGS = [
@@ -109,12 +119,22 @@ def flag_table():
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="TextBoost training on MI355X (HIP kernels behind the reference CLI).")
-    for name, kw in FLAGS + EXTENSION_FLAGS + ADAPTER_VARIANT_FLAGS:
+    for name, kw in FLAGS + EXTENSION_FLAGS + ADAPTER_VARIANT_FLAGS + MASKED_LOSS_FLAGS:
         kw = dict(kw)
         if "type" in kw:
             kw["type"] = _T[kw["type"]]
         p.add_argument(name, **kw)
     return p
+
+
+def check_mask_flags(args):
+    """--mask_floor is a weight in [0, 1) and means nothing without masks (a --concepts_list may name them per concept: data.concept_masks
+    checks that case once the list is read)"""
+    floor = float(getattr(args, "mask_floor", 0.0) or 0.0)
+    if not 0.0 <= floor < 1.0:
+        raise ValueError(f"--mask_floor {floor}: the background weight must satisfy 0 <= F < 1")
+    if floor != 0.0 and not getattr(args, "instance_mask_dir", None) and not getattr(args, "concepts_list", None):
+        raise ValueError("--mask_floor needs --instance_mask_dir: without masks there is no background to weigh")
 
 
 def parse_args(input_args=None):
@@ -136,6 +156,7 @@ def parse_args(input_args=None):
     if missing:  # q/k/v are one three-adapter kernel set, and the reference always trains them
         raise ValueError(f"--lora_target_modules must contain q_proj k_proj v_proj; {' '.join(missing)} missing")
     args.lora_target_modules = [m for m in LORA_TARGET_CHOICES if m in args.lora_target_modules]   # canonical order, duplicates dropped
+    check_mask_flags(args)
     if args.use_dora and args.lora_rank <= 0:
         raise ValueError("--use_dora needs --lora_rank > 0: DoRA decomposes the adapted weight, and --lora_rank 0 injects no adapter")
     return args

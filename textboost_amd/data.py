@@ -51,6 +51,78 @@ def decode_rgb(path: str) -> np.ndarray:
     return np.asarray(image)
 
 
+def instance_image_paths(data_root: str, max_samples: Optional[int] = None) -> List[str]:
+    """the files of `get_images_path` that are images: what the device feeder trains from"""
+    return [p for p in get_images_path(data_root, max_samples) if p.lower().endswith(IMAGE_EXTENSIONS)]
+
+
+def _pixel_size(path: str) -> Tuple[int, int]:
+    """(width, height) of a picture as `decode_rgb` hands it on (EXIF orientation applied); reads the header, and the pixels only to rotate"""
+    from PIL import Image, ImageOps
+    with Image.open(path) as im:
+        return ImageOps.exif_transpose(im).size
+
+
+def instance_mask_paths(image_paths: Sequence[str], mask_dir: str) -> List[str]:
+    """--instance_mask_dir: image <stem>.<ext> -> <mask_dir>/<stem>.<any of IMAGE_EXTENSIONS>, of the image's pixel size.  Host-only (file names
+    and headers), so that a run with a wrong mask directory ends before a device is touched.  ValueError names EVERY missing mask and
+    every mask of another size."""
+    if not os.path.isdir(mask_dir):
+        raise ValueError(f"--instance_mask_dir {mask_dir}: no such directory")
+    by_stem: Dict[str, str] = {}
+    for name in sorted(os.listdir(mask_dir)):
+        stem, ext = os.path.splitext(name)
+        if ext.lower() in IMAGE_EXTENSIONS:
+            by_stem.setdefault(stem, os.path.join(mask_dir, name))
+    out, missing, wrong = [], [], []
+    for p in image_paths:
+        m = by_stem.get(os.path.splitext(os.path.basename(p))[0])
+        if m is None:
+            missing.append(p)
+            continue
+        si, sm = _pixel_size(p), mask_size(m)
+        if si != sm:
+            wrong.append(f"{m} is {sm[0]} x {sm[1]}, {p} is {si[0]} x {si[1]}")
+        out.append(m)
+    if missing or wrong:
+        lines = [f"no mask in {mask_dir} for {p}" for p in missing] + wrong
+        raise ValueError("--instance_mask_dir: " + "; ".join(lines))
+    return out
+
+
+def mask_size(path: str) -> Tuple[int, int]:
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size
+
+
+def decode_mask(path: str) -> np.ndarray:
+    """a mask file -> uint8 [H, W], Pillow "L" (edit.load_mask): white = subject.  The bytes are used as they are, no threshold."""
+    from .edit import load_mask
+    return np.asarray(load_mask(path))
+
+
+def concept_masks(concepts, mask_floor: float = 0.0, max_samples: Optional[int] = None):
+    """Per concept the list of its mask paths (None for a concept that trains unmasked), from the concept's "instance_mask_dir" key (the
+    single concept built from the flags carries --instance_mask_dir there).  -> None when no concept has masks.  ValueError for a
+    --mask_floor without any mask, for a mask directory beside a data directory without image files, and (instance_mask_paths) for missing
+    or wrongly sized masks."""
+    out = []
+    for c in concepts:
+        d = c.get("instance_mask_dir") or None
+        if d is None:
+            out.append(None)
+            continue
+        if not has_instance_images(c.get("instance_data_dir")):
+            raise ValueError(f"instance_mask_dir {d}: {c.get('instance_data_dir')} holds no image files (tensor inputs take loss_weight.pt)")
+        out.append(instance_mask_paths(instance_image_paths(c["instance_data_dir"], max_samples), d))
+    if all(m is None for m in out):
+        if mask_floor:
+            raise ValueError("--mask_floor needs --instance_mask_dir (or an instance_mask_dir key in --concepts_list): no concept has masks")
+        return None
+    return out
+
+
 def multi_vector_names(token: str, n: int) -> List[str]:
     """utils.py:133-141: `<x>` -> `<x_0>`, `<x_1>`, ... when the initialiser has several BPE pieces."""
     if n == 1:

@@ -609,6 +609,39 @@ def mse_loss(pred, target, dpred, loss_out, loss_scale):
                                 L.stream()), "tb_mse_loss")
 
 
+_wmse_ws = {}
+
+
+def mse_loss_weighted_workspace(device, B, Cc, h, w):
+    """the partial sums of `mse_loss_weighted`, sized by the library, one buffer per (device, shape); TextBoostStep.enable_loss_weight asks for
+    it ahead of a capture"""
+    key = (torch.device(device), B, Cc, h, w)
+    ws = _wmse_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().tb_mse_loss_weighted_workspace_bytes(B, Cc, h, w)
+        if nbytes <= 0:
+            raise RuntimeError(f"tb_mse_loss_weighted_workspace_bytes failed with code {nbytes}")
+        ws = _wmse_ws[key] = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+    return ws
+
+
+def mse_loss_weighted(pred, target, weight, dpred, loss_out, loss_scale):
+    """the masked loss of --instance_mask_dir (csrc/masked_loss.hip): pred [B, C, h, w] (16-bit or fp32), target / dpred fp32 of that shape,
+    weight fp32 [B, 1, h, w] >= 0"""
+    B, Cc, h, w = pred.shape
+    assert tuple(weight.shape) == (B, 1, h, w) and weight.dtype == torch.float32, (weight.shape, weight.dtype)
+    assert all(t.dtype == torch.float32 and tuple(t.shape) == (B, Cc, h, w) for t in (target, dpred))
+    assert all(t.is_contiguous() for t in (pred, target, weight, dpred))
+    ws = mse_loss_weighted_workspace(pred.device, B, Cc, h, w)
+    if pred.dtype == torch.float32:
+        fn, name = L.lib().tb_mse_loss_weighted_f32, "tb_mse_loss_weighted_f32"
+    else:
+        assert _dt(pred) == L.TB_F16
+        fn, name = L.lib().tb_mse_loss_weighted, "tb_mse_loss_weighted"
+    L.check(fn(L.ptr(pred), L.ptr(target), L.ptr(weight), L.ptr(dpred), L.ptr(loss_out), L.ptr(loss_scale), B, Cc, h, w, L.ptr(ws),
+               ws.numel() * 4, L.stream()), name)
+
+
 def kpl_cos(h, h0, dh, partial, loss_out, loss_scale, weight):
     M, D = h.shape
     L.check(L.lib().tb_kpl_cos(L.ptr(h), h.stride(0), L.ptr(h0), h0.stride(0), _dt(h0), L.ptr(dh), dh.stride(0) if dh is not None else 0,
@@ -1089,6 +1122,15 @@ def img_to_pixels(src, x0, y0, dst):
     """dst: fp32 [3, R, R] (one slot of pixel_values)."""
     sh, sw = src.shape
     L.check(L.lib().tb_img_to_pixels(L.ptr(src), src.stride(0), sw, sh, x0, y0, L.ptr(dst), dst.shape[-1], L.stream()), "tb_img_to_pixels")
+
+
+def img_to_loss_weight(src, x0, y0, dst, cell=8, floor=0.0):
+    """dst: fp32 [..., out_h, out_w] (one slot of loss_weight) <- floor + (1 - floor) * box mean of the mask bytes over cell x cell pixels of
+    the crop of the grey RGBX mask image `src` at (x0, y0)."""
+    sh, sw = src.shape
+    assert dst.dtype == torch.float32 and dst.is_contiguous()
+    L.check(L.lib().tb_img_to_loss_weight(L.ptr(src), src.stride(0), sw, sh, x0, y0, dst.shape[-2], dst.shape[-1], cell, float(floor),
+                                          L.ptr(dst), L.stream()), "tb_img_to_loss_weight")
 
 
 def img_pack_rgb(rgb):

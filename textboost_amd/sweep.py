@@ -46,6 +46,7 @@ differences from the reference's driver:
   --fresh-process   one child `python train_textboost.py <argv>` per subject, as the reference does; default: every subject in this process on
                     models that stay on the device
   --resolution N / --seed N   passed on to every subject when given
+  --mask-root DIR   every subject gains --instance_mask_dir=DIR/<subject> (the masked loss); without it the argv is the reference's
   -g 0,1,...        several GPUs: one `python -m torch.distributed.run` of the sweep worker, every rank walks the same subjects
   exit status       non-zero when a subject failed; the failed subjects are listed at the end
 """
@@ -58,6 +59,8 @@ def _common_flags(p: argparse.ArgumentParser, subjects: str, data_dir: str):
     p.add_argument("--fresh-process", action="store_true", default=False, help="one child process per subject (the reference's form)")
     p.add_argument("--resolution", type=int, default=None, help="image side for every subject (default: by -m)")
     p.add_argument("--seed", type=int, default=None, help="--seed of every subject (default: train_textboost.py's own)")
+    p.add_argument("--mask-root", type=str, default=None, help="directory of the subjects' mask directories: every subject trains with "
+                   "--instance_mask_dir=DIR/<subject> (the masked loss; default: no masks, the reference's command line)")
 
 
 def db_parser() -> argparse.ArgumentParser:
@@ -147,7 +150,7 @@ def build_db(args) -> Tuple[str, List[Job]]:
                   resolution=RESOLUTION[key] if args.resolution is None else args.resolution)
     switches = ((args.num_samples is not None, "--num_samples={num_samples}"), (not args.no_inversion, "--augment_inversion"),
                 (args.no_weighted_sample, "--disable_weighted_sample"), (args.augment == "none", "--center_crop"), (args.mixing, "--mixing"),
-                (args.seed is not None, "--seed={seed}"))
+                (args.seed is not None, "--seed={seed}"), (args.mask_root is not None, "--instance_mask_dir={mask_root}/{name}"))
     jobs = []
     for s in load_subjects(args.subjects, ("name", "class_token", "initializer_token"), args.instances):
         jobs.append((s["name"], _fill(DB_ARGV, switches, dict(common, **s, data=os.path.join(args.data_dir, s["name"])))))
@@ -159,7 +162,8 @@ def build_sdrp(args) -> Tuple[str, List[Job]]:
     outdir = "output/tb_style-" + args.model + ("" if args.desc is None else f"-{args.desc}")
     common = dict(vars(args), outdir=outdir)
     switches = ((not args.no_inversion, "--augment_inversion"), (args.no_weighted_sample, "--disable_weighted_sample"),
-                (args.resolution is not None, "--resolution={resolution}"), (args.seed is not None, "--seed={seed}"))
+                (args.resolution is not None, "--resolution={resolution}"), (args.seed is not None, "--seed={seed}"),
+                (args.mask_root is not None, "--instance_mask_dir={mask_root}/{name}"))
     jobs = []
     for s in load_subjects(args.subjects, ("name", "template", "initializer_token"), args.instances):
         jobs.append((s["name"], _fill(SDRP_ARGV, switches, dict(common, **s, data=f"{args.data_dir}/{s['name']}"))))

@@ -279,6 +279,7 @@ class TextBoostStep:
                     o += n
                 self.grads_p = self.grads_p[:3] + (self.grads_p[3] if extra else {}, gm)
         self.vae = None  # attach_vae(): the step then starts from pixels (:1027-1037) instead of latents
+        self.loss_weight = None  # enable_loss_weight(): the masked loss's static input; None = the unmasked step, launch for launch
         self.fused_tail = os.environ.get("TB_OPT_TAIL", "1") == "1"   # the optimizer tail as two launches (round 6) instead of ten
         self.opt_ws = torch.zeros(132, device=device)
         self.lr_table = None  # set_lr_table(): lambda(k) of --lr_scheduler on the device, indexed by the successful-step count
@@ -291,6 +292,18 @@ class TextBoostStep:
         self.vae = vae
         self.pixel_values = torch.zeros(B, vae.geo.in_channels, vae.H, vae.W, device=self.dev)
         self.vae_eps = torch.zeros(B, C, h, w, device=self.dev)
+
+    def enable_loss_weight(self):
+        """The masked loss (--instance_mask_dir): `loss_weight` fp32 [B, 1, h, w] >= 0 becomes a static input of the step
+        (ones until the caller writes it) and the MSE node of every step body the weighted kernel.  Call it before `capture()`; each rank's
+        weights are its own, nothing new crosses ranks.  -> the buffer."""
+        if self.graph is not None:
+            raise RuntimeError("enable_loss_weight() after capture(): the captured step has the unmasked loss node")
+        if self.loss_weight is None:
+            B, _, h, w = self.x0.shape
+            self.loss_weight = torch.ones(B, 1, h, w, device=self.dev)
+            ops.mse_loss_weighted_workspace(self.loss_weight.device, B, self.x0.shape[1], h, w)   # allocated here, not inside a capture
+        return self.loss_weight
 
     # ------------------------------------------------------------------ pieces
     def draw(self):
@@ -336,7 +349,10 @@ class TextBoostStep:
         if self.accum == 1:  # (accumulating: the buffer is zeroed by `replay` / `step_eager` at the start of a cycle instead)
             self.flat_grad.zero_()  # every trainable gradient is accumulated into this buffer (UNet adapters here, the encoder's below)
         target = self.noise if hp.prediction_type == "epsilon" else self.velocity  # :1070-1075
-        ops.mse_loss(self.pred, target, self.dpred, st[L.ST_LOSS_MSE:], st[L.ST_LOSS_SCALE:])  # :1085-1090
+        if self.loss_weight is None:
+            ops.mse_loss(self.pred, target, self.dpred, st[L.ST_LOSS_MSE:], st[L.ST_LOSS_SCALE:])  # :1085-1090
+        else:  # the `mask is not None` branch (:1086-1088), with the weights at latent size and the division by C * max(W_b, 1)
+            ops.mse_loss_weighted(self.pred, target, self.loss_weight, self.dpred, st[L.ST_LOSS_MSE:], st[L.ST_LOSS_SCALE:])
         self.unet.backward(self.dpred, d_ehs_out=self.d_ehs)                       # :1108 (UNet part, dgrad only)
 
     def _phase_encoder_backward(self):

@@ -103,11 +103,27 @@ def _concepts(args):
             c.setdefault("initializer_token", args.initializer_token)
         return concepts
     return [{"instance_data_dir": args.instance_data_dir, "placeholder_token": args.placeholder_token,
-             "initializer_token": args.initializer_token}]
+             "initializer_token": args.initializer_token, "instance_mask_dir": getattr(args, "instance_mask_dir", None)}]
+
+
+def _loss_weight_tensor(args, partner):
+    """<instance_data_dir>/loss_weight.pt beside pixel_values.pt / latents.pt: the final fp32 [N, 1, h, w] weights of the masked loss (DESIGN.md
+    section 16), one per sample of its partner and of the latent size that follows from it; --mask_floor does not apply to it"""
+    path = os.path.join(args.instance_data_dir or "", "loss_weight.pt")
+    if partner is None or not os.path.exists(path):
+        return None
+    w = torch.load(path)
+    side = partner.shape[-1] // 8 if partner.shape[1] == 3 else partner.shape[-1]
+    if w.dtype != torch.float32 or tuple(w.shape) != (partner.shape[0], 1, side, side):
+        raise ValueError(f"{path}: expected fp32 [{partner.shape[0]}, 1, {side}, {side}] beside its partner, found {w.dtype} {list(w.shape)}")
+    if not bool(torch.isfinite(w).all()) or float(w.min()) < 0:
+        raise ValueError(f"{path}: loss weights must be finite and >= 0")
+    return w
 
 
 def _subject_inputs(args, have_tokenizer):
-    """What a subject trains from, and the latent side that follows from it -> (concepts, latents, pixels, use_images, latent)"""
+    """What a subject trains from, and the latent side that follows from it -> (concepts, latents, pixels, use_images, latent).  The masks of
+    --instance_mask_dir are checked here, on the host (file names and headers only)."""
     from textboost_amd import data as tbdata
     latent = args.resolution // 8
     lat_path = os.path.join(args.instance_data_dir or "", "latents.pt")
@@ -122,6 +138,7 @@ def _subject_inputs(args, have_tokenizer):
         latents, latent = None, pixels.shape[-1] // 8
     if latents is not None:
         latent = latents.shape[-1]
+    tbdata.concept_masks(concepts, getattr(args, "mask_floor", 0.0), args.num_samples)   # raises for a missing / wrongly sized mask
     return concepts, latents, pixels, use_images, latent
 
 
@@ -163,6 +180,10 @@ def setup_shared(args):
     if os.path.exists(ccfg):
         clip_geo = models.clip_geometry_from_config(json.load(open(ccfg)))
     check_resolution(args.resolution, unet_geo)
+    from textboost_amd import data as tbdata
+    from textboost_amd.cli import check_mask_flags
+    check_mask_flags(args)
+    tbdata.concept_masks(_concepts(args), getattr(args, "mask_floor", 0.0), args.num_samples)   # wrong masks end the run before the device is touched
     from textboost_amd.vae import VAEGeometry, vae_geometry_from_config
     vcfg = os.path.join(mdir, "vae", "config.json")
     vae_geo = vae_geometry_from_config(json.load(open(vcfg))) if os.path.exists(vcfg) else VAEGeometry()
@@ -454,6 +475,22 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
                 fh.handle(r)
         step.attach_vae(ctx.vae_encoder)
 
+    # ---- masked loss: subject masks beside the instance images, or ready weights beside the tensor inputs
+    mask_floor = float(getattr(args, "mask_floor", 0.0) or 0.0)
+    mask_paths = tbdata.concept_masks(concepts, mask_floor, args.num_samples)
+    if mask_paths is not None and not use_images:
+        raise ValueError("--instance_mask_dir needs a tokenizer and instance image files to train from; tensor inputs take loss_weight.pt")
+    loss_weights = None if use_images else _loss_weight_tensor(args, pixels if pixels is not None else latents)
+    if mask_paths is not None or loss_weights is not None:
+        step.enable_loss_weight()
+        if is_main:
+            if mask_paths is not None:
+                logger.info("masked loss: on, %d of %d concept(s) with --instance_mask_dir masks, --mask_floor %g (w = F + (1 - F) * mask, "
+                            "loss and gradient divided by C * max(sum w, 1) per sample)", sum(m is not None for m in mask_paths), len(concepts),
+                            mask_floor)
+            else:
+                logger.info("masked loss: on, weights from loss_weight.pt %s (--mask_floor does not apply)", list(loss_weights.shape))
+
     # ---- data: latents (+ ids) from disk, else synthetic; rank r takes samples r, r+W, ... (every shard non-empty: SURVEY 0.6)
     dg = torch.Generator().manual_seed(1000 + rank)
     ids_path = os.path.join(args.instance_data_dir or "", "input_ids.pt")
@@ -475,11 +512,16 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
                                             inversion=args.augment_inversion, p=args.augment_p, ops=args.augment_ops)
         # the reference formats the template with the LIST of placeholder names (`concept["instance_token"] = placeholder_tokens`, :691-692)
         images = []
-        for c, names in zip(concepts, concept_names):  # dataset.py:302-308: every concept's images, each with that concept's token list
-            paths = [p for p in tbdata.get_images_path(c["instance_data_dir"], args.num_samples) if p.lower().endswith(tbdata.IMAGE_EXTENSIONS)]
-            images += [(tbaug.to_device_image(tbdata.decode_rgb(p)), names) for p in paths]
+        for ci, (c, names) in enumerate(zip(concepts, concept_names)):  # dataset.py:302-308: every concept's images, each with that concept's token list
+            paths = tbdata.instance_image_paths(c["instance_data_dir"], args.num_samples)
+            if mask_paths is None:
+                images += [(tbaug.to_device_image(tbdata.decode_rgb(p)), names) for p in paths]
+            else:  # a concept without masks in a masked run: None here, an all-white mask in the feeder
+                mp = mask_paths[ci] if mask_paths[ci] is not None else [None] * len(paths)
+                images += [(tbaug.to_device_image(tbdata.decode_rgb(p)), names, None if m is None else tbaug.to_device_mask(tbdata.decode_mask(m)))
+                           for p, m in zip(paths, mp)]
         feeder = tbaug.DeviceFeeder(images, tokenizer, tbdata.load_templates(args.template), size=args.resolution,
-                                    center_crop=args.center_crop, augment_pipe=pipe)
+                                    center_crop=args.center_crop, augment_pipe=pipe, mask_floor=mask_floor)
         index_stream = tbdata.IndexStream(len(images), args.seed or 0, rank, world)
         if args.seed is not None:  # set_seed(args.seed) (:601) also seeds `random` and numpy, which the augmentation draws from
             pyrandom.seed(args.seed)
@@ -509,11 +551,15 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
         elif pixels is not None:
             idx = shard_indices(pixels.shape[0], B, it, rank, world)
             step.pixel_values.copy_(pixels[idx])
+            if loss_weights is not None:
+                step.loss_weight.copy_(loss_weights[idx])
             if inst_ids is not None:
                 step.input_ids.copy_(inst_ids[[i % inst_ids.shape[0] for i in idx]])
         elif latents is not None:
             idx = shard_indices(latents.shape[0], B, it, rank, world)
             step.x0.copy_(latents[idx])
+            if loss_weights is not None:
+                step.loss_weight.copy_(loss_weights[idx])
             if inst_ids is not None:
                 step.input_ids.copy_(inst_ids[[i % inst_ids.shape[0] for i in idx]])
         else:
@@ -595,7 +641,7 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
     spent["capture"] = time.perf_counter() - t_cap
     if feeder is not None:  # batch k+1 is produced on a side stream while step k runs (augment.PrefetchFeeder)
         from textboost_amd.augment import PrefetchFeeder
-        prefetcher = PrefetchFeeder(feeder, B, step.pixel_values, step.input_ids)
+        prefetcher = PrefetchFeeder(feeder, B, step.pixel_values, step.input_ids, loss_weight=step.loss_weight if feeder.has_mask else None)
         prefetcher.prefetch(index_stream.take(B))
     t0 = time.perf_counter()
     G = args.gradient_accumulation_steps
