@@ -13,6 +13,18 @@
  *  - `stream` is a hipStream_t; all work is enqueued on it (graph-capture safe).
  *  - activations are row-major 2-D [rows, channels] with an explicit row stride `ld*` in ELEMENTS
  *    (UNet: NHWC, rows = b*H*W + y*W + x); fp16 unless stated; statistics/optimizer state fp32.
+ *
+ * This file is also the source of the Python binding: textboost_amd/_abi.py reads it when the package is imported and raises on anything
+ * outside the subset of C below (tests/test_abi_host.py checks the result against the C compiler).  A new declaration keeps to it:
+ *  - comments are block comments; preprocessor lines are skipped, except `#define TB_NAME <integer>`; no line continuations.
+ *  - `typedef struct [tag] { ... } name;` with fields `type a, b, c;` -- the `*` belongs to the type (`float* p; float* q;`, not
+ *    `float *p, *q;`); no arrays, bit-fields, nested structs or unions.
+ *  - prototypes `ret name(type name, ...);` or `ret name(void);`, name = tb_*: every parameter named, structs passed as `const tb_x_desc*` only; a stream is the LAST
+ *    parameter (the Python wrappers append it).
+ *  - `enum { TB_NAME = <integer>, ... };` with every value explicit.
+ *  - types: int, int32_t, int64_t, uint32_t, float, double, tb_stream_t, pointers to those and to void / char / uint8_t, and the structs
+ *    declared above the use.  Every pointer binds as an untyped address, except descriptors and `int32_t*` struct FIELDS (host integers
+ *    the library writes, tb_gemm_desc.split_out).
  */
 #ifndef TEXTBOOST_HIP_H
 #define TEXTBOOST_HIP_H
