@@ -632,6 +632,36 @@ int tb_attention_rel_fwd(const tb_attn_desc* d, const float* rel, const int32_t*
  * hg TB_F16 [M, 2F] (the stacked [wi_0 ; wi_1] projection), out TB_F16 [M, F]. */
 int tb_gated_gelu_tanh(const void* hg, int64_t ldh, void* out, int64_t ldo, int64_t M, int F, tb_stream_t stream);
 
+/* ---- subject masks from cross-attention (csrc/auto_mask.hip; textboost_amd/auto_mask.py, make_masks.py, inference.py --mask auto:WORD;
+ * DESIGN.md section 17) -------------------------------------------------------------------------------------------------------------------
+ * The chain from the accumulators of tb_attn_token_maps to mask bytes at a photo's pixel size: fp32 / u8 / u32 only, the same in both builds.
+ * Every output element has one owner or is an integer sum: a repeated launch is bit-identical.
+ *
+ * tb_map_word_upsample: acc fp32 [nb, T, h * w] (one resolution's accumulator), positions HOST int32 [npos] (a word's token positions; read
+ * during the call, so the caller need not keep them), 1 <= npos <= T <= 128, every position in [0, T), h, w <= 128.
+ *   m[i][j] = sum_b sum_p acc[b][positions[p]][i * w + j]                 (fp32, summed in index order)
+ *   score[y][x] (+)= weight * bilinear(m)(y, x)                           score fp32 [H, W], any H, W >= 1 (H * W < 2^31)
+ * bilinear = F.interpolate(mode="bilinear", align_corners=False), no antialiasing: source coordinate (dst + 0.5) (h / H) - 0.5 clamped at 0
+ * (formed in float64, its fraction rounded to fp32 once), upper neighbour clamped at h - 1; the same in x.  accumulate = 0 overwrites
+ * `score`, 1 adds to it.  Anything else returns -22 and launches nothing. */
+int tb_map_word_upsample(const float* acc, int nb, int T, int h, int w, const int32_t* positions /* host [npos] */, int npos, float weight,
+                         float* score, int H, int W, int accumulate, tb_stream_t stream);
+/* minmax[0] = min, minmax[1] = max of score[0 .. n), n >= 1, finite values (exact: the order of a min / max does not matter).  ws: 512 floats
+ * of scratch for the two-stage form (at most 256 workgroups, then one), or NULL: one workgroup. */
+int tb_score_range(const float* score, int64_t n, float* minmax, float* ws /* >= 512 floats, or NULL */, tb_stream_t stream);
+/* hist u32 [256], cleared here: with (lo, hi) = minmax, t = (s - lo) / (hi - lo) as one rounded fp32 subtraction over another and one rounded
+ * division (t = 0 when hi == lo), bin = min(255, (int)(t * 256)).  LDS counters per workgroup, then integer adds: exact. */
+int tb_score_hist(const float* score, int64_t n, const float* minmax, uint32_t* hist, tb_stream_t stream);
+/* Otsu's threshold of hist u32 [256], one workgroup.  N = sum h_i, S = sum i h_i, w0(k) = sum_{i<=k} h_i, s0(k) = sum_{i<=k} i h_i (exact
+ * integers); c(k) = (S w0 - N s0)^2 / (w0 (N - w0)) in float64, every operation rounded on its own, over the k with 0 < w0 < N; k = the
+ * smallest k of maximal c.  thr[0] = (k + 1) / 256 (exact), thr[1] = k.  No such k (all mass in one bin): thr = (1, 255), nothing is foreground. */
+int tb_otsu_threshold(const uint32_t* hist, float* thr /* [2] */, tb_stream_t stream);
+/* mask u8 [n] from t of tb_score_hist: soft = 0: t >= thr[0] ? 255 : 0;  soft = 1: (u8) rint(255 clamp(t, 0, 1)), round half to even. */
+int tb_mask_from_score(const float* score, const float* minmax, const float* thr, uint8_t* mask, int64_t n, int soft, tb_stream_t stream);
+/* out[y][x] = max of in over the (2 radius + 1)^2 square around (x, y), clipped at the borders; u8 [H, W] contiguous, in != out,
+ * 0 <= radius <= 64 (0 copies).  One pass: a 64 x 64 tile and its halo in LDS, rows then columns. */
+int tb_mask_dilate(const uint8_t* in, uint8_t* out, int W, int H, int radius, tb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 textboost_amd/generate.py.
 
     python inference.py <output_dir> --model <diffusers model dir> --prompt "photo of a <dog> dog" [--seeds 0 1 2 3] [--output grid.jpg]
-        [--checkpoint N] [--with <output_dir> ...] [--weights W ...] [--init-image photo.jpg [--strength S] [--mask mask.png [--no-paste]]]
+        [--checkpoint N] [--with <output_dir> ...] [--weights W ...]
+        [--init-image photo.jpg [--strength S] [--mask mask.png | --mask auto:WORD [--dilate PX]] [--no-paste]]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -29,7 +30,10 @@ resolution with Lanczos, centre crop), is encoded once by the VAE encoder (the d
 (0, 1] selects (default 0.8): the last int(steps * S) steps run, each seed's latent being its image's noise.  --mask FILE (the photo's size;
 white = repaint) keeps everything else: after every step the unmasked latent cells are reset to the photo's at that noise level, and the
 decoded region is pasted into the prepared photo, so pixels outside the mask are the photo's bytes (--no-paste writes the plain decode).  One
-photo and one mask serve all --seeds; --with, --weights, --checkpoint and --attn-map work as before.
+photo and one mask serve all --seeds; --with, --weights, --checkpoint and --attn-map work as before.  --mask auto:WORD makes the mask from the
+photo instead of reading a file (textboost_amd/auto_mask.py): where WORD ("sofa", "dog") attends in the noised photo, on the
+pipeline's own UNet (2 x seeds rows, all conditional) with the run's text encoder, thresholded by Otsu's method at the photo's size and grown
+by --dilate PX pixels; it is also written as `<output stem>_mask.png`.  A mask without a white pixel ends the run: nothing would be edited.
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
@@ -70,7 +74,10 @@ def build_parser():
     p.add_argument("--strength", type=float, default=None, metavar="S",
                    help=f"with --init-image: how much of the schedule runs, in (0, 1] (default {DEFAULT_STRENGTH})")
     p.add_argument("--mask", type=str, default=None, metavar="FILE",
-                   help="with --init-image: repaint only where this picture (same size as the photo) is white")
+                   help="with --init-image: repaint only where this picture (same size as the photo) is white; auto:WORD makes the mask from "
+                        "the photo: where WORD attends in it")
+    p.add_argument("--dilate", type=int, default=None, metavar="PX",
+                   help="with --mask auto:WORD: grow the mask by a square of this radius in the photo's pixels (default 0)")
     p.add_argument("--no-paste", dest="no_paste", action="store_true",
                    help="with --mask: write the plain decode instead of pasting the repainted region into the photo")
     return p
@@ -118,10 +125,11 @@ def load_runs(args):
 
 def check_edit_args(args):
     """--init-image / --strength / --mask: every refusal, on the host.  -> None (text-to-image) or {"rgb": uint8 [H, W, 3], "mask": PIL "L" image
-    or None, "strength": float}"""
+    or None, "strength": float, "auto": the word of --mask auto:WORD or None, "dilate": int}"""
+    from textboost_amd import auto_mask as A
     from textboost_amd import edit as E
     if args.init_image is None:
-        for flag, given in (("--mask", args.mask is not None), ("--strength", args.strength is not None)):
+        for flag, given in (("--mask", args.mask is not None), ("--strength", args.strength is not None), ("--dilate", args.dilate is not None)):
             if given:
                 raise SystemExit(f"inference.py: {flag} needs --init-image FILE (the photo to edit)")
         return None
@@ -134,8 +142,16 @@ def check_edit_args(args):
         rgb = E.load_rgb(args.init_image)
     except (OSError, ValueError) as e:
         raise SystemExit(f"inference.py: --init-image {args.init_image}: cannot be read as a picture ({e})")
-    mask = None
+    mask = auto = None
     if args.mask is not None:
+        try:
+            kind, auto = A.parse_auto_mask(args.mask)
+        except ValueError as e:
+            raise SystemExit(f"inference.py: --mask {args.mask}: {e}")
+        auto = auto if kind == "auto" else None
+    if args.dilate is not None and (auto is None or not 0 <= args.dilate <= A.MAX_DILATE):
+        raise SystemExit(f"inference.py: --dilate PX goes with --mask auto:WORD, 0 .. {A.MAX_DILATE} pixels")
+    if args.mask is not None and auto is None:
         try:
             mask = E.load_mask(args.mask)
         except (OSError, ValueError) as e:
@@ -147,7 +163,19 @@ def check_edit_args(args):
         E.check_vae_has_encoder(args.model)
     except (OSError, ValueError) as e:
         raise SystemExit(f"inference.py: --init-image: {e}")
-    return {"rgb": rgb, "mask": mask, "strength": strength}
+    return {"rgb": rgb, "mask": mask, "strength": strength, "auto": auto, "dilate": args.dilate or 0}
+
+
+def check_auto_mask(pixel_mask, word):
+    """the prepared pixel mask of --mask auto:WORD must repaint something: an all-black one would write the photo back unedited"""
+    if not pixel_mask.any():
+        raise SystemExit(f"inference.py: --mask auto:{word}: the mask has no white pixel inside the prepared photo (the attention to {word!r} "
+                         "is flat, or its region lies outside the centre crop): nothing would be edited; paint a mask and pass --mask FILE")
+
+
+def auto_mask_path(args):
+    stem = os.path.splitext(args.output)[0] if args.output is not None else args.prompt.replace(" ", "_")
+    return stem + "_mask.png"
 
 
 def attn_map_words(model_dir, run, prompt, requested):
@@ -218,6 +246,21 @@ def main(argv=None):
         base = G.load_base_text(args.model)
         te, tokenizer = G.load_text_encoder(args.model, run, 2 * n, base=base)
         pipe.set_run(run)
+        enc = None
+        if edit is not None and edit["auto"] is not None:      # before the prompts are encoded: the maker runs the same text encoder
+            from PIL import Image
+            from textboost_amd import auto_mask as A
+            from textboost_amd import edit as E
+            enc = E.EditEncoder(args.model, pipe.size)
+            maker = A.MaskMaker(pipe.unet, enc, lambda i: te.forward(i, pins=False), tokenizer, pipe.sampler.sch.alphas_cumprod)
+            try:
+                auto_mask, stats = maker.mask(edit["rgb"], edit["auto"], dilate=edit["dilate"])
+            except ValueError as e:
+                raise SystemExit(f"inference.py: --mask auto:{edit['auto']}: {e}")
+            edit["mask"] = Image.fromarray(auto_mask.cpu().numpy())
+            edit["mask"].save(auto_mask_path(args))
+            print(f"wrote {auto_mask_path(args)}: {A.describe(auto_mask, stats)}")
+            del maker
         T = base.geo.max_pos
         ids = G.tokenize(tokenizer, [""] * n + [args.prompt] * n, T).to(pipe.dev)
         states = te.forward(ids, pins=False).view(2, n * T, -1)
@@ -232,13 +275,15 @@ def main(argv=None):
         else:       # a seed's latent is the noise of its image; the photo is encoded once
             import numpy as np
             from textboost_amd import edit as E
-            enc = E.EditEncoder(args.model, pipe.size)
+            enc = enc or E.EditEncoder(args.model, pipe.size)
             init_rgbx, pixels = E.prepare_image(edit["rgb"], enc.S)
             z0 = enc.encode(pixels)
             del enc
             latent_mask = pixel_mask = None
             if edit["mask"] is not None:
                 pm, lm = E.prepare_mask(edit["mask"], init_rgbx.shape[0], cell=init_rgbx.shape[0] // pipe.size)
+                if edit["auto"] is not None:
+                    check_auto_mask(pm, edit["auto"])
                 latent_mask = torch.from_numpy(np.ascontiguousarray(lm)).to(pipe.dev)
                 if not args.no_paste:
                     pixel_mask = torch.from_numpy(np.ascontiguousarray(pm)).to(pipe.dev)

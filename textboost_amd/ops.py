@@ -1140,3 +1140,61 @@ def gated_gelu_tanh(hg, out):
     with _rec("gated_gelu_kernel", 0.0, float(M * F * 3 * 2)):
         _launch("tb_gated_gelu_tanh", L.ptr(hg), hg.stride(0), L.ptr(out), out.stride(0), M, F)
     return out
+
+
+# ------------------------------------------------------------------ subject masks from cross-attention (csrc/auto_mask.hip; auto_mask.py)
+SCORE_RANGE_WS = 512   # floats of scratch of the two-stage tb_score_range
+
+
+def map_word_upsample(acc, h, w, positions, weight, score, accumulate=False):
+    """score[H, W] (+)= weight * bilinear(sum over images and over the word's token `positions` of acc)(y, x): acc fp32 [nb, T, h * w] (one
+    accumulator of an `AttnMapRecorder`), positions a host sequence of ints, score fp32 [H, W] contiguous.  F.interpolate's bilinear,
+    align_corners=False."""
+    nb, T, n = acc.shape
+    H, W = score.shape
+    assert acc.dtype == torch.float32 and acc.is_contiguous() and n == h * w, (acc.dtype, tuple(acc.shape), h, w)
+    assert score.dtype == torch.float32 and score.is_contiguous()
+    pos = (ctypes.c_int32 * len(positions))(*[int(p) for p in positions])
+    _launch("tb_map_word_upsample", L.ptr(acc), nb, T, h, w, pos, len(positions), float(weight), L.ptr(score), H, W, int(accumulate))
+    return score
+
+
+def score_range(score, minmax, ws=None):
+    """minmax[0], minmax[1] = min, max of the fp32 tensor `score`; ws: SCORE_RANGE_WS floats (two-stage) or None (one workgroup)"""
+    assert score.dtype == torch.float32 and score.is_contiguous() and minmax.dtype == torch.float32 and minmax.numel() >= 2
+    assert ws is None or (ws.dtype == torch.float32 and ws.numel() >= SCORE_RANGE_WS)
+    _launch("tb_score_range", L.ptr(score), score.numel(), L.ptr(minmax), L.ptr(ws))
+    return minmax
+
+
+def score_hist(score, minmax, hist):
+    """hist int32 [256] (read as u32; cleared by the call) of (score - lo) / (hi - lo) in 256 bins"""
+    assert score.dtype == torch.float32 and score.is_contiguous() and hist.dtype == torch.int32 and hist.numel() == 256 and hist.is_contiguous()
+    _launch("tb_score_hist", L.ptr(score), score.numel(), L.ptr(minmax), L.ptr(hist))
+    return hist
+
+
+def otsu_threshold(hist, thr):
+    """thr[0] = (k + 1) / 256, thr[1] = k: Otsu's bin k of hist int32 [256]"""
+    assert hist.dtype == torch.int32 and hist.numel() == 256 and hist.is_contiguous() and thr.dtype == torch.float32 and thr.numel() >= 2
+    _launch("tb_otsu_threshold", L.ptr(hist), L.ptr(thr))
+    return thr
+
+
+def mask_from_score(score, minmax, thr, mask, soft=False):
+    """mask uint8 (score's shape): hard = 255 where the normalised score reaches thr[0]; soft = rint(255 * normalised score)"""
+    assert score.dtype == torch.float32 and score.is_contiguous() and mask.dtype == torch.uint8 and mask.is_contiguous()
+    assert mask.numel() == score.numel()
+    _launch("tb_mask_from_score", L.ptr(score), L.ptr(minmax), L.ptr(thr), L.ptr(mask), score.numel(), int(bool(soft)))
+    return mask
+
+
+def mask_dilate(mask, radius, out=None):
+    """uint8 [H, W] -> its maximum over the (2 radius + 1)^2 square, clipped at the borders (a new tensor unless `out` is given)"""
+    H, W = mask.shape
+    assert mask.dtype == torch.uint8 and mask.is_contiguous()
+    if out is None:
+        out = torch.empty_like(mask)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (H, W)
+    _launch("tb_mask_dilate", L.ptr(mask), L.ptr(out), W, H, int(radius))
+    return out
