@@ -464,6 +464,7 @@ enum { TB_ST_LOSS_SCALE = 0, TB_ST_GROWTH_TRACKER = 1, TB_ST_STEP = 2, TB_ST_FOU
        TB_ST_LOSS_MSE = 11, TB_ST_LOSS_KPL = 12,
        TB_ST_LR_MULT = 13, /* lr_scheduler (diffusers get_scheduler, :911-916): holds lambda(step) - 1, written by the host or by tb_lr_from_table, so a zeroed
                               state means the constant schedule; every group's lr = base lr * (1 + state[13]) */
+       TB_ST_LOSS_ATTN = 14, /* L_attn of the step, unscaled (tb_attn_loss_final; --attn_loss_weight) */
        TB_ST_COUNT = 16 };
 int tb_sumsq(const float* x, int64_t n, float* out, float* ws64 /* 64 floats scratch */, tb_stream_t stream);
 /* GradScaler unscale/inf-check/update + clip_grad_norm_ coefficient + Adam bias corrections (:1108, :1128-1134).  grad_div >= 1 is the
@@ -604,6 +605,29 @@ int tb_mse_loss_weighted(const void* pred, const float* target, const float* wei
                          int B, int C, int h, int w, float* ws, int64_t ws_bytes, tb_stream_t stream);
 int tb_mse_loss_weighted_f32(const float* pred, const float* target, const float* weight, float* dpred, float* loss_out,
                              const float* loss_scale, int B, int C, int h, int w, float* ws, int64_t ws_bytes, tb_stream_t stream);
+
+/* ---- cross-attention localisation loss (csrc/attn_loss.hip; --attn_loss_weight) -------------------------------------
+ * With p_{b,h,s,j} = softmax_j(scale q_{b,h,s} . k_{b,h,j}), P_J = sum_j tok_w[b,j] p_j and A_{b,s} = (1/H) sum_h P_J, a layer's loss is
+ * sum_b sum_s g[b,s] A_{b,s}; the step's L_attn is the mean over the batch and the supervised layers.
+ *
+ * tb_attn_loss_coef: target fp32 [B, 1, h, w] (the subject mask on the latent grid) -> g fp32 [B, (h / f) (w / f)] for a layer whose map is
+ * f times smaller: m = f x f box mean, fg = sum_s m, bg = sum_s (1 - m), g = (1 - m) / max(bg, 1) - m / max(fg, 1).  One workgroup per sample,
+ * sums in double in a fixed order, one rounding at the end (|g| <= 1).  h % f == 0, w % f == 0, 1 <= f <= 64. */
+int tb_attn_loss_coef(const float* target, int B, int h, int w, int f, float* g, tb_stream_t stream);
+/* tb_attn_loss_bwd: reads B, H, Sq, Skv, hd, scale, Q / ldq, K / ldk (as tb_attn_token_maps) and dQ / lddq, dK / lddk of the descriptor, and
+ * ADDS the loss's gradient to dQ and dK in the operand dtype, each element as rounded(float(old) + add), once, by one owning lane:
+ *   ds_j = p_j (c g_s / H) (tok_w_j - P_J),  c = coef * loss_scale[0]      dq_s += scale sum_j ds_j k_j      dk_j += scale sum_s ds_{s,j} q_s
+ * tok_w fp32 [B, Skv], g fp32 [B, Sq] (|g| < 63), coef = lambda / (B * number of supervised layers), loss_scale may be NULL (= 1).
+ * ws is [n_slots][slot_floats] floats (tb_attn_loss_workspace_bytes(B, H, n_slots) with the largest H of the layers; slot_floats = that B * H):
+ * the launch writes sum_s g_s P_J / H of every (batch, head) to the first B * H floats of slot `slot` and zeros to the rest of the slot.  A
+ * sample whose tok_w is all zero leaves its rows of dQ / dK untouched, and an element whose addend is zero is not stored (-0 stays -0).  No atomics: a repeated launch on the same inputs is bit-identical.
+ * dtype TB_F16 only; hd % 8 == 0, hd <= 160, 1 <= Skv <= 128, any Sq, any leading dimension >= H * hd and any row alignment; anything else,
+ * or a workspace shorter than (slot + 1) * slot_floats floats, returns -22 and launches nothing. */
+int64_t tb_attn_loss_workspace_bytes(int B, int H, int n_slots);
+int tb_attn_loss_bwd(const tb_attn_desc* d, int dtype, const float* tok_w, const float* g, float coef, const float* loss_scale, float* ws,
+                     int64_t ws_bytes, int slot, int64_t slot_floats, tb_stream_t stream);
+/* out[0] = norm * (sum of the n_slots * slot_floats partials, in double, in a fixed order): state[TB_ST_LOSS_ATTN] with norm = 1 / (B * n_slots) */
+int tb_attn_loss_final(const float* ws, int n_slots, int64_t slot_floats, float norm, float* out, tb_stream_t stream);
 
 /* ---- CLIP ViT patch embedding (csrc/clip_vision.hip; the image tower of the CLIP-T / CLIP-I evaluation, textboost_amd/clip_score.py) -------
  * img: B resident RGBX images of S x S pixels, image b at img + b * img_stride, rows row_stride pixels apart.  P = (S / patch)^2 patches.

@@ -352,12 +352,14 @@ class DeviceFeeder:
     "pixel_values": fp32 [B, 3, size, size] on the device, "prompts": list[str]} and, when any image carries a mask, "loss_weight": fp32
     [B, 1, size / 8, size / 8]: the mask after the image's augmentation, Lanczos resize and crop, box-averaged over the VAE's 8 x 8 cells,
     w = mask_floor + (1 - mask_floor) * mean / 255.  An image without a mask in such a run gets an all-white one (it trains unmasked).  The
-    mask draws nothing: pixel_values, prompts and the random streams are those of the same feeder without masks."""
+    mask draws nothing: pixel_values, prompts and the random streams are those of the same feeder without masks.  attn_target = True (the
+    localisation loss) adds "attn_target": the same pooling of the same crop with floor 0 -- the very tensor of
+    "loss_weight" when mask_floor is 0."""
 
     LATENT_CELL = 8   # pixels per latent cell of every supported VAE
 
     def __init__(self, images: Sequence[tuple], tokenizer, templates: Sequence[str], size=512, center_crop=False,
-                 augment_pipe: Optional[PairedAugmentation] = None, mask_floor: float = 0.0):
+                 augment_pipe: Optional[PairedAugmentation] = None, mask_floor: float = 0.0, attn_target: bool = False):
         if len(images) == 0:
             raise ValueError("no instance images")
         if not 0.0 <= mask_floor < 1.0:
@@ -374,6 +376,9 @@ class DeviceFeeder:
         self.images = [(im, tok) for im, tok, _ in items]
         self.masks = [m for _, _, m in items] if self.has_mask else None
         self.mask_floor = float(mask_floor)
+        if attn_target and not self.has_mask:
+            raise ValueError("attn_target needs masks: no image of this feeder carries one")
+        self.attn_target = bool(attn_target)
         self.templates = list(templates)
         self.size = size
         self.center_crop = center_crop
@@ -383,9 +388,9 @@ class DeviceFeeder:
     def __len__(self):
         return len(self.images)
 
-    def item_into(self, index: int, dst: torch.Tensor, weight_dst: Optional[torch.Tensor] = None):
-        """One sample; pixel_values written into dst [3, size, size] and, with masks, the loss weights into weight_dst [1, size/8, size/8].
-        Returns (input_ids [1, 77], prompt)."""
+    def item_into(self, index: int, dst: torch.Tensor, weight_dst: Optional[torch.Tensor] = None, target_dst: Optional[torch.Tensor] = None):
+        """One sample; pixel_values written into dst [3, size, size] and, with masks, the loss weights into weight_dst [1, size/8, size/8] (and
+        their floor-0 form into target_dst when given).  Returns (input_ids [1, 77], prompt)."""
         image, instance_token = self.images[index % len(self.images)]
         mask = self.masks[index % len(self.images)] if self.has_mask else None
         if self.has_mask and weight_dst is None:
@@ -409,23 +414,31 @@ class DeviceFeeder:
         ops.img_to_pixels(image, x1, y1, dst)
         if mask is not None:
             ops.img_to_loss_weight(mask, x1, y1, weight_dst, cell=self.LATENT_CELL, floor=self.mask_floor)
+            if target_dst is not None:
+                ops.img_to_loss_weight(mask, x1, y1, target_dst, cell=self.LATENT_CELL, floor=0.0)
         return self.tokenize(prompt), prompt
 
-    def batch(self, indices: Sequence[int], out: Optional[torch.Tensor] = None, weight_out: Optional[torch.Tensor] = None):
+    def batch(self, indices: Sequence[int], out: Optional[torch.Tensor] = None, weight_out: Optional[torch.Tensor] = None,
+              target_out: Optional[torch.Tensor] = None):
         B = len(indices)
         dev = self.images[0][0].device
         if out is None:
             out = torch.empty(B, 3, self.size, self.size, dtype=torch.float32, device=dev)
         if self.has_mask and weight_out is None:
             weight_out = torch.empty(B, 1, self.size // self.LATENT_CELL, self.size // self.LATENT_CELL, dtype=torch.float32, device=dev)
+        second = self.attn_target and self.mask_floor != 0.0   # (floor 0: the target IS the weights)
+        if second and target_out is None:
+            target_out = torch.empty_like(weight_out)
         ids, prompts = [], []
         for b, i in enumerate(indices):
-            t, p = self.item_into(i, out[b], weight_out[b] if self.has_mask else None)
+            t, p = self.item_into(i, out[b], weight_out[b] if self.has_mask else None, target_out[b] if second else None)
             ids.append(t)
             prompts.append(p)
         res = {"input_ids": torch.cat(ids, dim=0), "pixel_values": out, "prompts": prompts}
         if self.has_mask:
             res["loss_weight"] = weight_out
+        if self.attn_target:
+            res["attn_target"] = target_out if second else weight_out
         return res
 
 
@@ -436,13 +449,17 @@ class PrefetchFeeder:
     stream wait for it and copies pixels / ids into the step's static inputs (one device-to-device copy)."""
 
     def __init__(self, feeder: DeviceFeeder, batch: int, pixel_values: torch.Tensor, input_ids: torch.Tensor,
-                 loss_weight: Optional[torch.Tensor] = None):
+                 loss_weight: Optional[torch.Tensor] = None, attn_target: Optional[torch.Tensor] = None):
         self.feeder, self.batch = feeder, batch
         self.pixel_values, self.input_ids = pixel_values, input_ids
         if (loss_weight is not None) != bool(getattr(feeder, "has_mask", False)):
             raise ValueError("a feeder with masks needs the step's loss_weight input, and one without must not be given it")
         self.loss_weight = loss_weight   # the masked loss's static input (TextBoostStep.enable_loss_weight), staged beside the pixels
         self.weight_staging = torch.empty_like(loss_weight) if loss_weight is not None else None
+        if (attn_target is not None) != bool(getattr(feeder, "attn_target", False)):
+            raise ValueError("a feeder with attn_target needs the step's attn_target input, and one without must not be given it")
+        self.attn_target = attn_target   # the localisation loss's static input (TextBoostStep.enable_attn_loss), staged beside the weights
+        self.target_staging = torch.empty_like(attn_target) if attn_target is not None and feeder.mask_floor != 0.0 else None
         self.staging = torch.empty_like(pixel_values)
         self.ids_staging = torch.empty_like(input_ids)
         self.side = torch.cuda.Stream(device=pixel_values.device)
@@ -456,8 +473,10 @@ class PrefetchFeeder:
         with torch.cuda.stream(self.side):
             if self.loss_weight is None:   # (the call of a run without masks is what it was)
                 b = self.feeder.batch(indices, out=self.staging)
-            else:
+            elif self.target_staging is None:
                 b = self.feeder.batch(indices, out=self.staging, weight_out=self.weight_staging)
+            else:
+                b = self.feeder.batch(indices, out=self.staging, weight_out=self.weight_staging, target_out=self.target_staging)
             self.ids_staging.copy_(b["input_ids"], non_blocking=True)
             self.ready.record(self.side)
         self.pending = b
@@ -471,6 +490,8 @@ class PrefetchFeeder:
         self.input_ids.copy_(self.ids_staging)
         if self.loss_weight is not None:
             self.loss_weight.copy_(self.weight_staging)
+        if self.attn_target is not None:
+            self.attn_target.copy_(self.target_staging if self.target_staging is not None else self.weight_staging)
         self.consumed = torch.cuda.Event()
         self.consumed.record(torch.cuda.current_stream())
         b, self.pending = self.pending, None

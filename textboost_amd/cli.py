@@ -100,6 +100,15 @@ MASKED_LOSS_FLAGS = [
     ("--mask_floor", dict(type="float", default=0.0, help=(
         "loss weight F of a background pixel, 0 <= F < 1: w = F + (1 - F) * mask.  Needs --instance_mask_dir; does not apply to loss_weight.pt"))),
 ]
+# cross-attention localisation loss (FastComposer's supervision of where the placeholder token attends): off by default
+ATTN_LOSS_FLAGS = [
+    ("--attn_loss_weight", dict(type="float", default=0.0, help=(
+        "weight of the cross-attention localisation loss (0 = off): loss = mse + kpl_weight * kpl + W * L_attn, L_attn in [-1, 1] lowest when all "
+        "the attention mass of the placeholder token lies on the subject mask.  Needs --instance_mask_dir and --mixed_precision fp16 or bf16"))),
+    ("--attn_loss_levels", dict(type="int", nargs="+", default=[2], metavar="L", help=(
+        "UNet levels whose cross-attention layers are supervised (0 = the latent grid; default 2: the 16 x 16 maps at 512 x 512, five layers "
+        "on SD1.x)"))),
+]
 # the adapter's variants (also not the reference's).  --use_dora: peft's LoraConfig(use_dora=True) -- every adapted Linear also trains a magnitude
 # per output row; needs --lora_rank > 0
 ADAPTER_VARIANT_FLAGS = [
@@ -119,7 +128,7 @@ def flag_table():
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="TextBoost training on MI355X (HIP kernels behind the reference CLI).")
-    for name, kw in FLAGS + EXTENSION_FLAGS + ADAPTER_VARIANT_FLAGS + MASKED_LOSS_FLAGS:
+    for name, kw in FLAGS + EXTENSION_FLAGS + ADAPTER_VARIANT_FLAGS + MASKED_LOSS_FLAGS + ATTN_LOSS_FLAGS:
         kw = dict(kw)
         if "type" in kw:
             kw["type"] = _T[kw["type"]]
@@ -135,6 +144,35 @@ def check_mask_flags(args):
         raise ValueError(f"--mask_floor {floor}: the background weight must satisfy 0 <= F < 1")
     if floor != 0.0 and not getattr(args, "instance_mask_dir", None) and not getattr(args, "concepts_list", None):
         raise ValueError("--mask_floor needs --instance_mask_dir: without masks there is no background to weigh")
+
+
+def attn_loss_weight_of(args) -> float:
+    """--attn_loss_weight as a float >= 0 (nan refused); parse_args runs it, so a bad weight never leaves the command line"""
+    raw = getattr(args, "attn_loss_weight", 0.0)
+    w = float(0.0 if raw is None else raw)
+    if not w >= 0.0:
+        raise ValueError(f"--attn_loss_weight {raw}: the weight must be >= 0")
+    return w
+
+
+def check_attn_loss_flags(args, cross_attn_levels=None):
+    """--attn_loss_weight: >= 0; when on it needs masks (--instance_mask_dir, or the key in a --concepts_list: data.concept_masks checks that
+    case once the list is read), a 16-bit mode, and levels the UNet has (`cross_attn_levels`: one bool per UNet level, when known)"""
+    w = attn_loss_weight_of(args)
+    if w == 0.0:
+        return
+    levels = list(getattr(args, "attn_loss_levels", None) or [2])
+    if any(l < 0 for l in levels):
+        raise ValueError(f"--attn_loss_levels {levels}: levels are counted from 0, the latent grid")
+    if cross_attn_levels is not None:
+        bad = [l for l in levels if l >= len(cross_attn_levels) or not cross_attn_levels[l]]
+        if bad:
+            have = [i for i, on in enumerate(cross_attn_levels) if on]
+            raise ValueError(f"--attn_loss_levels {bad}: this UNet has cross-attention on levels {have} only")
+    if not getattr(args, "instance_mask_dir", None) and not getattr(args, "concepts_list", None):
+        raise ValueError("--attn_loss_weight needs --instance_mask_dir: the loss is told where the subject is by its masks")
+    if getattr(args, "mixed_precision", None) in (None, "no"):
+        raise NotImplementedError("--attn_loss_weight without --mixed_precision: the localisation loss has 16-bit kernels only (fp16 or bf16)")
 
 
 def parse_args(input_args=None):
@@ -157,6 +195,7 @@ def parse_args(input_args=None):
         raise ValueError(f"--lora_target_modules must contain q_proj k_proj v_proj; {' '.join(missing)} missing")
     args.lora_target_modules = [m for m in LORA_TARGET_CHOICES if m in args.lora_target_modules]   # canonical order, duplicates dropped
     check_mask_flags(args)
+    attn_loss_weight_of(args)
     if args.use_dora and args.lora_rank <= 0:
         raise ValueError("--use_dora needs --lora_rank > 0: DoRA decomposes the adapted weight, and --lora_rank 0 injects no adapter")
     return args

@@ -612,6 +612,48 @@ def mse_loss_weighted(pred, target, weight, dpred, loss_out, loss_scale):
             L.ptr(dpred), L.ptr(loss_out), L.ptr(loss_scale), B, Cc, h, w, L.ptr(ws), ws.numel() * 4)
 
 
+def attn_loss_coef(target, g, factor):
+    """g[b, s] = (1 - m) / max(bg_b, 1) - m / max(fg_b, 1) with m the factor x factor box mean of target fp32 [B, 1, h, w] (the subject mask on
+    the latent grid): the coefficients of the cross-attention localisation loss for a layer whose map is `factor` times smaller
+    (csrc/attn_loss.hip).  g fp32 [B, (h / factor) * (w / factor)]."""
+    B, one, h, w = target.shape
+    assert one == 1 and target.dtype == torch.float32 and target.is_contiguous(), (tuple(target.shape), target.dtype)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() * factor * factor == B * h * w, (tuple(g.shape), factor)
+    _launch("tb_attn_loss_coef", L.ptr(target), B, h, w, factor, L.ptr(g))
+    return g
+
+
+def attn_loss_workspace(device, B, H, n_slots):
+    """the partial sums of `attn_loss_bwd`, one slot of B * H floats per supervised layer (H: the largest head count among them)"""
+    nbytes = L.lib().tb_attn_loss_workspace_bytes(B, H, n_slots)
+    if nbytes <= 0:
+        raise RuntimeError(f"tb_attn_loss_workspace_bytes failed with code {nbytes}")
+    return torch.zeros(n_slots, nbytes // (4 * n_slots), device=device, dtype=torch.float32)
+
+
+def attn_loss_bwd(q, k, dq, dk, tok_w, g, B, H, Sq, Skv, hd, coef, loss_scale, ws, slot, scale=None):
+    """The cross-attention localisation loss of one layer (csrc/attn_loss.hip): recomputes softmax(scale q k^T), ADDS the loss's gradient to
+    dq [B*Sq, H*hd] and dk [B*Skv, H*hd] (the library's half type, column slices allowed) and writes the layer's partial loss sums to ws[slot].
+    tok_w fp32 [B, Skv], g fp32 [B, Sq], coef = lambda / (B * supervised layers), loss_scale a one-element fp32 tensor or None."""
+    assert q.dtype == k.dtype == dq.dtype == dk.dtype and all(t.stride(1) == 1 for t in (q, k, dq, dk))
+    assert tok_w.dtype == torch.float32 and tok_w.is_contiguous() and tok_w.numel() == B * Skv, (tuple(tok_w.shape), B, Skv)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() == B * Sq, (tuple(g.shape), B, Sq)
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.dim() == 2
+    d = L.AttnDesc()
+    d.B, d.H, d.Sq, d.Skv, d.hd, d.causal, d.scale = B, H, Sq, Skv, hd, 0, scale if scale is not None else hd ** -0.5
+    d.Q, d.ldq = L.ptr(q), q.stride(0)
+    d.K, d.ldk = L.ptr(k), k.stride(0)
+    d.dQ, d.lddq = L.ptr(dq), dq.stride(0)
+    d.dK, d.lddk = L.ptr(dk), dk.stride(0)
+    with _rec("attn_loss_bwd_kernel", 14.0 * B * H * Sq * Skv * hd):
+        _launch("tb_attn_loss_bwd", d, _dt(q), L.ptr(tok_w), L.ptr(g), coef, L.ptr(loss_scale), L.ptr(ws), ws.numel() * 4, slot, ws.shape[1])
+
+
+def attn_loss_final(ws, norm, out):
+    """out[0] = norm * sum(ws) in a fixed order: L_attn of the step with norm = 1 / (B * supervised layers)"""
+    _launch("tb_attn_loss_final", L.ptr(ws), ws.shape[0], ws.shape[1], norm, L.ptr(out))
+
+
 def kpl_cos(h, h0, dh, partial, loss_out, loss_scale, weight):
     M, D = h.shape
     _launch("tb_kpl_cos", L.ptr(h), h.stride(0), L.ptr(h0), h0.stride(0), _dt(h0), L.ptr(dh), dh.stride(0) if dh is not None else 0,

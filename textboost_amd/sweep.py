@@ -47,6 +47,8 @@ differences from the reference's driver:
                     models that stay on the device
   --resolution N / --seed N   passed on to every subject when given
   --mask-root DIR   every subject gains --instance_mask_dir=DIR/<subject> (the masked loss); without it the argv is the reference's
+  --attn-loss-weight W   every subject gains --attn_loss_weight=W (the localisation loss, with --mask-root; run_textboost_db.py only: the
+                    StyleDrop sweep is fp32 and refuses it); without it nothing is added
   -g 0,1,...        several GPUs: one `python -m torch.distributed.run` of the sweep worker, every rank walks the same subjects
   exit status       non-zero when a subject failed; the failed subjects are listed at the end
 """
@@ -61,6 +63,8 @@ def _common_flags(p: argparse.ArgumentParser, subjects: str, data_dir: str):
     p.add_argument("--seed", type=int, default=None, help="--seed of every subject (default: train_textboost.py's own)")
     p.add_argument("--mask-root", type=str, default=None, help="directory of the subjects' mask directories: every subject trains with "
                    "--instance_mask_dir=DIR/<subject> (the masked loss; default: no masks, the reference's command line)")
+    p.add_argument("--attn-loss-weight", type=float, default=None, help="--attn_loss_weight of every subject (the cross-attention localisation "
+                   "loss; needs --mask-root; the StyleDrop sweep trains in fp32 and refuses the switch); default: not passed on")
 
 
 def db_parser() -> argparse.ArgumentParser:
@@ -150,7 +154,8 @@ def build_db(args) -> Tuple[str, List[Job]]:
                   resolution=RESOLUTION[key] if args.resolution is None else args.resolution)
     switches = ((args.num_samples is not None, "--num_samples={num_samples}"), (not args.no_inversion, "--augment_inversion"),
                 (args.no_weighted_sample, "--disable_weighted_sample"), (args.augment == "none", "--center_crop"), (args.mixing, "--mixing"),
-                (args.seed is not None, "--seed={seed}"), (args.mask_root is not None, "--instance_mask_dir={mask_root}/{name}"))
+                (args.seed is not None, "--seed={seed}"), (args.mask_root is not None, "--instance_mask_dir={mask_root}/{name}"),
+                (args.attn_loss_weight is not None, "--attn_loss_weight={attn_loss_weight}"))
     jobs = []
     for s in load_subjects(args.subjects, ("name", "class_token", "initializer_token"), args.instances):
         jobs.append((s["name"], _fill(DB_ARGV, switches, dict(common, **s, data=os.path.join(args.data_dir, s["name"])))))
@@ -159,6 +164,9 @@ def build_db(args) -> Tuple[str, List[Job]]:
 
 def build_sdrp(args) -> Tuple[str, List[Job]]:
     """-> (output directory, [(subject, argv)]) of the StyleDrop sweep: no --mixed_precision (fp32), the subject's own prompt template"""
+    if args.attn_loss_weight is not None:   # (here, on the host, before any subject starts: every one of them would raise in setup_shared)
+        raise SystemExit("--attn-loss-weight: the StyleDrop sweep trains without --mixed_precision (fp32), and the localisation loss has 16-bit "
+                         "kernels only; use it on run_textboost_db.py")
     outdir = "output/tb_style-" + args.model + ("" if args.desc is None else f"-{args.desc}")
     common = dict(vars(args), outdir=outdir)
     switches = ((not args.no_inversion, "--augment_inversion"), (args.no_weighted_sample, "--disable_weighted_sample"),

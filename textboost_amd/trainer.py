@@ -280,6 +280,8 @@ class TextBoostStep:
                 self.grads_p = self.grads_p[:3] + (self.grads_p[3] if extra else {}, gm)
         self.vae = None  # attach_vae(): the step then starts from pixels (:1027-1037) instead of latents
         self.loss_weight = None  # enable_loss_weight(): the masked loss's static input; None = the unmasked step, launch for launch
+        self.attn_loss = None    # enable_attn_loss(): the localisation loss's settings; None = no launch, no buffer, no graph node
+        self.attn_target = None  # ... and its static input, the subject mask on the latent grid
         self.fused_tail = os.environ.get("TB_OPT_TAIL", "1") == "1"   # the optimizer tail as two launches (round 6) instead of ten
         self.opt_ws = torch.zeros(132, device=device)
         self.lr_table = None  # set_lr_table(): lambda(k) of --lr_scheduler on the device, indexed by the successful-step count
@@ -304,6 +306,30 @@ class TextBoostStep:
             self.loss_weight = torch.ones(B, 1, h, w, device=self.dev)
             ops.mse_loss_weighted_workspace(self.loss_weight.device, B, self.x0.shape[1], h, w)   # allocated here, not inside a capture
         return self.loss_weight
+
+    def enable_attn_loss(self, weight: float, levels, placeholder_ids):
+        """The cross-attention localisation loss (--attn_loss_weight): the step's loss becomes mse + kpl_weight * kpl +
+        weight * L_attn, with L_attn in [-1, 1] lowest when all the attention mass of the placeholder token lies on the subject.
+        `placeholder_ids` = (first, end) is the id range of the placeholder token's vectors; `attn_tok_w` is made from the step's static
+        `input_ids` inside the step.  `attn_target` fp32 [B, 1, h, w] (floor 0; ones until the caller writes it) becomes a static input.  Call
+        it before `capture()`; each rank's targets are its own, nothing new crosses ranks.  -> the buffer."""
+        if self.graph is not None:
+            raise RuntimeError("enable_attn_loss() after capture(): the captured step has no localisation-loss nodes")
+        if self.unet.dtype == torch.float32:
+            raise NotImplementedError("--attn_loss_weight: the localisation loss has 16-bit kernels only; use --mixed_precision fp16 or bf16")
+        if not weight >= 0:
+            raise ValueError(f"attn loss weight {weight}: must be >= 0")
+        lo, hi = (int(x) for x in placeholder_ids)
+        assert lo < hi
+        al = self.unet.enable_attn_loss(levels, weight)
+        al.loss_scale = self.state[L.ST_LOSS_SCALE:]
+        B, T = self.input_ids.shape
+        al.ids = (lo, hi)
+        al.ge = torch.zeros(B, T, dtype=torch.bool, device=self.dev)
+        al.lt = torch.zeros(B, T, dtype=torch.bool, device=self.dev)
+        self.attn_loss = al
+        self.attn_target = self.unet.attn_target
+        return self.attn_target
 
     # ------------------------------------------------------------------ pieces
     def draw(self):
@@ -353,7 +379,14 @@ class TextBoostStep:
             ops.mse_loss(self.pred, target, self.dpred, st[L.ST_LOSS_MSE:], st[L.ST_LOSS_SCALE:])  # :1085-1090
         else:  # the `mask is not None` branch (:1086-1088), with the weights at latent size and the division by C * max(W_b, 1)
             ops.mse_loss_weighted(self.pred, target, self.loss_weight, self.dpred, st[L.ST_LOSS_MSE:], st[L.ST_LOSS_SCALE:])
+        al = self.attn_loss
+        if al is not None:  # tok_w[b, j] = 1 where input_ids[b, j] is one of the placeholder token's vectors (torch ops: plumbing)
+            torch.ge(self.input_ids, al.ids[0], out=al.ge)
+            torch.lt(self.input_ids, al.ids[1], out=al.lt)
+            torch.mul(al.ge, al.lt, out=self.unet.attn_tok_w)
         self.unet.backward(self.dpred, d_ehs_out=self.d_ehs)                       # :1108 (UNet part, dgrad only)
+        if al is not None:
+            self.unet.attn_loss_final(st[L.ST_LOSS_ATTN:])
 
     def _phase_encoder_backward(self):
         hp, te = self.hp, self.te
@@ -628,7 +661,13 @@ class TextBoostStep:
 
     # ------------------------------------------------------------------ host-side reads (NOT in the hot loop)
     def scalars(self):
+        """the step's scalars; `loss_attn` (and its term in `loss`) only when enable_attn_loss() was called: a step without the localisation loss
+        reports the keys and the values it always did"""
         s = self.state.tolist()
-        return {"loss_mse": s[L.ST_LOSS_MSE], "loss_kpl": s[L.ST_LOSS_KPL],
-                "loss": s[L.ST_LOSS_MSE] + self.hp.kpl_weight * s[L.ST_LOSS_KPL], "loss_scale": s[L.ST_LOSS_SCALE],
-                "grad_norm": s[L.ST_GRAD_NORM], "found_inf": s[L.ST_FOUND_INF], "opt_steps": s[L.ST_STEP]}
+        sc = {"loss_mse": s[L.ST_LOSS_MSE], "loss_kpl": s[L.ST_LOSS_KPL],
+              "loss": s[L.ST_LOSS_MSE] + self.hp.kpl_weight * s[L.ST_LOSS_KPL], "loss_scale": s[L.ST_LOSS_SCALE],
+              "grad_norm": s[L.ST_GRAD_NORM], "found_inf": s[L.ST_FOUND_INF], "opt_steps": s[L.ST_STEP]}
+        if self.attn_loss is not None:
+            sc["loss_attn"] = s[L.ST_LOSS_ATTN]
+            sc["loss"] += self.attn_loss.weight * s[L.ST_LOSS_ATTN]
+        return sc

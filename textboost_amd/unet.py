@@ -18,6 +18,7 @@ buffers, the layer schedule and the weight re-packing:
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -139,6 +140,7 @@ class HipUNet:
         self.attn_fp8 = attn_fp8
         self._fp8_ws = None
         self.attn_maps = None   # an attn_maps.AttnMapRecorder: every cross-attention forward then also records its token maps (opt-in; None = no launch)
+        self.attn_loss = None   # enable_attn_loss(): the cross-attention localisation loss in the backward of the supervised layers (None = no launch)
         self._bufs: Dict[str, torch.Tensor] = {}
         self.tape: List = []
         self._pack(state_dict)
@@ -160,6 +162,37 @@ class HipUNet:
     def scratch(self, tag, rows, cols, dtype=None):
         dtype = self.dtype if dtype is None else dtype
         return self.buf(f"scr.{tag}.{rows}x{cols}.{dtype}", rows, cols, dtype)
+
+    # ------------------------------------------------------------------ cross-attention localisation loss
+    def enable_attn_loss(self, levels, weight: float):
+        """--attn_loss_weight: the backward of every cross-attention layer whose map lies on one of `levels` (UNet levels: 0 = the latent grid)
+        adds the gradient of weight * L_attn to its dq / dk (csrc/attn_loss.hip), one launch per layer, plus one coefficient launch per level
+        ahead of the first of them.  Static inputs, to be written before a step: `attn_target` fp32 [B, 1, h, w] (the subject mask on the latent
+        grid, ones until then) and `attn_tok_w` fp32 [B, T] (1 at the placeholder token's positions, zeros until then).  `loss_scale` (a one-element
+        fp32 tensor, or None = 1) is set by the caller; `attn_loss_final(out)` reduces the step's partials to L_attn.  Call it before a capture:
+        every buffer is allocated here."""
+        assert self.dtype != torch.float32, "the localisation loss has 16-bit kernels only"
+        levels = sorted(set(int(l) for l in levels))
+        layers = [p for p, _ in self.xattn if self.xattn_level[p] in levels]
+        for l in levels:
+            if not any(self.xattn_level[p] == l for p in layers):
+                raise ValueError(f"attn loss level {l}: this UNet has cross-attention on levels "
+                                 f"{sorted(set(self.xattn_level.values()))} only")
+        B, dev = self.B, self.dev
+        al = SimpleNamespace(levels=levels, weight=float(weight), slot={p: i for i, p in enumerate(layers)}, n=len(layers), loss_scale=None)
+        al.coef = al.weight / (B * al.n)
+        al.g = {l: torch.zeros(B, (self.H >> l) * (self.W >> l), device=dev) for l in levels}
+        al.ws = ops.attn_loss_workspace(dev, B, max(self.geo.heads(self.xattn_level[p]) for p in layers), al.n)
+        al.coef_done = set()      # levels whose coefficients this backward has computed already
+        self.attn_target = torch.ones(B, 1, self.H, self.W, device=dev)
+        self.attn_tok_w = torch.zeros(B, self.T, device=dev)
+        self.attn_loss = al
+        return al
+
+    def attn_loss_final(self, out):
+        """out[0] = L_attn of the last backward (unscaled; the mean over the batch and the supervised layers)"""
+        al = self.attn_loss
+        ops.attn_loss_final(al.ws, 1.0 / (self.B * al.n), out)
 
     # ------------------------------------------------------------------ cross-attention K/V adapters (SURVEY 8(f).4)
     def enable_kv_lora(self, r: int, alpha: Optional[float] = None, seed: Optional[int] = None):
@@ -244,6 +277,7 @@ class HipUNet:
         ch = geo.block_out_channels
         self.resnets: List[str] = []
         self.xattn: List[Tuple[str, int]] = []   # (prefix of attn2, C)
+        self.xattn_level: Dict[str, int] = {}    # prefix of attn2 -> UNet level of its map
         self._walk = []
         # conv_in / conv_out as boundary kernels (4-channel NCHW side)
         w = _f32v(sd["conv_in.weight"], dev)                     # [C0,4,3,3]
@@ -275,6 +309,7 @@ class HipUNet:
             lin(f"{tb}.attn1.to_out.0")
             lin(f"{tb}.attn2.to_out.0")
             self.xattn.append((f"{tb}.attn2", C))
+            self.xattn_level[f"{tb}.attn2"] = level
             wff = pack_geglu_rows(sd[f"{tb}.ff.net.0.proj.weight"])
             bff = pack_geglu_rows(sd[f"{tb}.ff.net.0.proj.bias"])
             lin(f"{tb}.ff.net.2")
@@ -581,6 +616,13 @@ class HipUNet:
             dk2, dv2 = self.dkv_all[:, ko:ko + C], self.dkv_all[:, ko + C:ko + 2 * C]
             xws = self.scratch("xattn_ws", 16 * 2 * B * T, C, torch.float32) if self.dtype != torch.float32 else None
             ops.attention_bwd(q2, k2, v2, o2, lse2, do2, delta, dq2, dk2, dv2, B, heads, HW, T, hd, ws=xws)
+            al = self.attn_loss
+            if al is not None and level in al.levels:   # the localisation loss of this layer: its gradient joins dq2 / dk2
+                if level not in al.coef_done:
+                    ops.attn_loss_coef(self.attn_target, al.g[level], 1 << level)
+                    al.coef_done.add(level)
+                ops.attn_loss_bwd(q2, k2, dq2, dk2, self.attn_tok_w, al.g[level], B, heads, HW, T, hd, al.coef, al.loss_scale, al.ws,
+                                  al.slot[tb + ".attn2"])
             if stop_after_cross:
                 return
             dt1 = self.scratch("g4", M, C)
@@ -780,6 +822,8 @@ class HipUNet:
     # ------------------------------------------------------------------ backward (dgrad only, down to d_ehs)
     def backward(self, dpred, d_ehs_out=None):
         S, geo, B, P = self._saved, self.geo, self.B, self.P
+        if self.attn_loss is not None:
+            self.attn_loss.coef_done.clear()
         ch = geo.block_out_channels
         nl = len(ch)
         hw, Ms = S["hw"], S["Ms"]

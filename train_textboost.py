@@ -181,9 +181,12 @@ def setup_shared(args):
         clip_geo = models.clip_geometry_from_config(json.load(open(ccfg)))
     check_resolution(args.resolution, unet_geo)
     from textboost_amd import data as tbdata
-    from textboost_amd.cli import check_mask_flags
+    from textboost_amd.cli import check_attn_loss_flags, check_mask_flags
     check_mask_flags(args)
-    tbdata.concept_masks(_concepts(args), getattr(args, "mask_floor", 0.0), args.num_samples)   # wrong masks end the run before the device is touched
+    check_attn_loss_flags(args, unet_geo.cross_attn_levels)
+    have_masks = tbdata.concept_masks(_concepts(args), getattr(args, "mask_floor", 0.0), args.num_samples)   # wrong masks end the run before the device is touched
+    if float(getattr(args, "attn_loss_weight", 0.0) or 0.0) > 0 and have_masks is None:
+        raise ValueError("--attn_loss_weight needs masks (--instance_mask_dir, or an instance_mask_dir key in --concepts_list): no concept has any")
     from textboost_amd.vae import VAEGeometry, vae_geometry_from_config
     vcfg = os.path.join(mdir, "vae", "config.json")
     vae_geo = vae_geometry_from_config(json.load(open(vcfg))) if os.path.exists(vcfg) else VAEGeometry()
@@ -491,6 +494,21 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
             else:
                 logger.info("masked loss: on, weights from loss_weight.pt %s (--mask_floor does not apply)", list(loss_weights.shape))
 
+    # ---- cross-attention localisation loss: the same masks, floor 0, tell the placeholder token where to attend
+    attn_w = float(getattr(args, "attn_loss_weight", 0.0) or 0.0)
+    if attn_w > 0:
+        if mask_paths is None:
+            raise ValueError("--attn_loss_weight needs --instance_mask_dir masks beside instance image files; tensor inputs (latents.pt / "
+                             "pixel_values.pt with loss_weight.pt) carry no localisation target")
+        place_ids = sorted(added_tokens.values())
+        assert place_ids == list(range(place_ids[0], place_ids[0] + len(place_ids))), place_ids
+        attn_levels = sorted(set(getattr(args, "attn_loss_levels", None) or [2]))
+        step.enable_attn_loss(attn_w, attn_levels, (place_ids[0], place_ids[-1] + 1))
+        if is_main:
+            logger.info("attention loss: on, --attn_loss_weight %g, --attn_loss_levels %s (%d cross-attention layer(s)), placeholder ids %d..%d; "
+                        "loss = mse + kpl_weight * kpl + W * L_attn", attn_w, " ".join(map(str, attn_levels)), step.attn_loss.n, place_ids[0],
+                        place_ids[-1])
+
     # ---- data: latents (+ ids) from disk, else synthetic; rank r takes samples r, r+W, ... (every shard non-empty: SURVEY 0.6)
     dg = torch.Generator().manual_seed(1000 + rank)
     ids_path = os.path.join(args.instance_data_dir or "", "input_ids.pt")
@@ -521,7 +539,7 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
                 images += [(tbaug.to_device_image(tbdata.decode_rgb(p)), names, None if m is None else tbaug.to_device_mask(tbdata.decode_mask(m)))
                            for p, m in zip(paths, mp)]
         feeder = tbaug.DeviceFeeder(images, tokenizer, tbdata.load_templates(args.template), size=args.resolution,
-                                    center_crop=args.center_crop, augment_pipe=pipe, mask_floor=mask_floor)
+                                    center_crop=args.center_crop, augment_pipe=pipe, mask_floor=mask_floor, attn_target=attn_w > 0)
         index_stream = tbdata.IndexStream(len(images), args.seed or 0, rank, world)
         if args.seed is not None:  # set_seed(args.seed) (:601) also seeds `random` and numpy, which the augmentation draws from
             pyrandom.seed(args.seed)
@@ -641,7 +659,8 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
     spent["capture"] = time.perf_counter() - t_cap
     if feeder is not None:  # batch k+1 is produced on a side stream while step k runs (augment.PrefetchFeeder)
         from textboost_amd.augment import PrefetchFeeder
-        prefetcher = PrefetchFeeder(feeder, B, step.pixel_values, step.input_ids, loss_weight=step.loss_weight if feeder.has_mask else None)
+        prefetcher = PrefetchFeeder(feeder, B, step.pixel_values, step.input_ids, loss_weight=step.loss_weight if feeder.has_mask else None,
+                                    attn_target=step.attn_target if feeder.attn_target else None)
         prefetcher.prefetch(index_stream.take(B))
     t0 = time.perf_counter()
     G = args.gradient_accumulation_steps
@@ -656,8 +675,12 @@ def _train_subject_in_mode(ctx, args, final, fh, val_ids):
         done = it + 1
         if is_main and (done % 50 == 0 or done == args.max_train_steps):  # scalars are read off the hot loop
             sc = step.scalars()
-            logger.info("step %d loss %.6f mse %.6f kpl %.6f scale %.0f grad_norm %.4f", done, sc["loss"], sc["loss_mse"],
-                        sc["loss_kpl"], sc["loss_scale"], sc["grad_norm"])
+            if step.attn_loss is None:
+                logger.info("step %d loss %.6f mse %.6f kpl %.6f scale %.0f grad_norm %.4f", done, sc["loss"], sc["loss_mse"],
+                            sc["loss_kpl"], sc["loss_scale"], sc["grad_norm"])
+            else:
+                logger.info("step %d loss %.6f mse %.6f kpl %.6f loss_attn %.6f scale %.0f grad_norm %.4f", done, sc["loss"], sc["loss_mse"],
+                            sc["loss_kpl"], sc["loss_attn"], sc["loss_scale"], sc["grad_norm"])
             print(f"step {done}: loss {sc['loss']:.5f} lr {args.learning_rate}", flush=True)
         if sampler is not None and done % args.validation_steps == 0:  # :1212-1228
             t_val = time.perf_counter()
