@@ -319,6 +319,18 @@ int tb_attention_set_variant(int bits);
  * operands' (TB_F16 only).  accumulate = 0 overwrites `maps`, 1 adds to it (no atomics: each element has one owner, so a launch is
  * bit-reproducible).  hd % 8 == 0, hd <= 160, 1 <= Skv <= 128, any Sq; anything else returns -22 and launches nothing. */
 int tb_attn_token_maps(const tb_attn_desc* d, int dtype, int b0, int nb, float w, int accumulate, float* maps, tb_stream_t stream);
+/* Regional cross-attention forward (csrc/region_attn.hip): tb_attention_fwd's O = softmax_j(scale q . k_j + m[s][j]) V on a short key sequence,
+ * with the mask of regional prompting,
+ *   m[s][j] = 0 if key_region[b][j] < 0 (an unrestricted key) or bit key_region[b][j] of query_regions[s] is set, -inf otherwise:
+ * key j of batch row b is visible only to the queries inside its region.  key_region int32 [B, Skv] (device; regions 0 .. 31; per batch row, so
+ * the unconditional half of a guided batch is all -1), query_regions uint32 [Sq] (device; bit r = query s lies in region r; shared by all
+ * batch rows and heads).  A masked probability is an exact zero; a query whose keys are all masked gets O = 0 and LSE = -inf (no NaN).
+ * Reads Q / K / V / O, their leading dimensions (any >= H * hd, any row alignment), LSE (may be NULL), B, H, Sq, Skv, hd and scale of the
+ * descriptor.  dtype is the operands' (TB_F16 only); hd % 8 == 0, hd <= 160, 1 <= Skv <= 128, any Sq, causal == 0; anything else -- a NULL
+ * table and a key_region value >= 32 included -- returns -22 and launches nothing.  The key_region values are read back and checked
+ * (one small copy behind the stream's queued work) unless the stream is being captured, where nothing may synchronise: the kernel then
+ * treats a value >= 32 as a region no query belongs to.  No atomics, every output has one owner: a repeated launch is bit-identical. */
+int tb_attention_region_fwd(const tb_attn_desc* d, int dtype, const int32_t* key_region, const uint32_t* query_regions, tb_stream_t stream);
 
 /* ---- scheduler / boundary / loss / misc streaming kernels ------------------------------------------ */
 /* noise_scheduler.add_noise (:1052) [+ get_velocity (:1073) when velocity != NULL]; fp32 NCHW in, fp16 noisy out */

@@ -5,6 +5,7 @@ textboost_amd/generate.py.
     python inference.py <output_dir> --model <diffusers model dir> --prompt "photo of a <dog> dog" [--seeds 0 1 2 3] [--output grid.jpg]
         [--checkpoint N] [--with <output_dir> ...] [--weights W ...]
         [--init-image photo.jpg [--strength S] [--mask mask.png | --mask auto:WORD [--dilate PX]] [--no-paste]]
+        [--region "WORDS=x0,y0,x1,y1" | --region "WORDS=@mask.png" ...] [--region-steps F]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -34,6 +35,16 @@ photo and one mask serve all --seeds; --with, --weights, --checkpoint and --attn
 photo instead of reading a file (textboost_amd/auto_mask.py): where WORD ("sofa", "dog") attends in the noised photo, on the
 pipeline's own UNet (2 x seeds rows, all conditional) with the run's text encoder, thresholded by Otsu's method at the photo's size and grown
 by --dilate PX pixels; it is also written as `<output stem>_mask.png`.  A mask without a white pixel ends the run: nothing would be edited.
+
+--region "WORDS=x0,y0,x1,y1" (repeatable, at most 32) confines words of the prompt to a part of the picture (textboost_amd/regions.py,
+DESIGN.md 19): `--prompt "a <dog> dog and a <cat> cat" --region "<dog> dog=0,0,0.5,1" --region "<cat> cat=0.5,0,1,1"` puts the dog on the left
+and the cat on the right.  WORDS are one or more space-separated words of the prompt; in every cross-attention layer their tokens are then
+visible only to the image positions inside the box (fractions of the image, 0 <= x0 < x1 <= 1; a latent cell is inside if its centre is),
+all other tokens stay global, and the unconditional half of the guidance batch is untouched.  `WORDS=@mask.png` takes a picture of any
+size instead of a box (resized to the latent grid, white = inside).  --region-steps F in (0, 1] lets the regions act on the first
+ceil(F * executed steps) steps only (default: all).  `<output stem>_regions.png` shows the regions as flat colours at the image's size.
+Works with --with and with --init-image / --mask; not with --attn-map (the recorder recomputes an unmasked softmax and would report
+attention that did not happen).
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
@@ -80,6 +91,10 @@ def build_parser():
                    help="with --mask auto:WORD: grow the mask by a square of this radius in the photo's pixels (default 0)")
     p.add_argument("--no-paste", dest="no_paste", action="store_true",
                    help="with --mask: write the plain decode instead of pasting the repainted region into the photo")
+    p.add_argument("--region", dest="region", type=str, action="append", default=None, metavar="WORDS=BOX",
+                   help="confine these words of the prompt to a box x0,y0,x1,y1 (fractions of the image) or to @mask.png; repeatable")
+    p.add_argument("--region-steps", dest="region_steps", type=float, default=None, metavar="F",
+                   help="with --region: the regions act on the first ceil(F * executed steps) steps, 0 < F <= 1 (default 1)")
     return p
 
 
@@ -116,7 +131,8 @@ def load_runs(args):
         for n, _ in r.tokens:
             first.setdefault(n, r.path)
     for tok, dropped in run.shadowed:
-        for what, text in [("--prompt", args.prompt)] + [("--attn-map", w) for w in (args.attn_map or [])]:
+        for what, text in [("--prompt", args.prompt)] + [("--attn-map", w) for w in (args.attn_map or [])] + \
+                [("--region", r) for r in (getattr(args, "region", None) or [])]:
             if tok in text:
                 raise SystemExit(f"inference.py: {what} {text!r} uses {tok}, which both {first[tok]} and {dropped} hold: ambiguous (the first "
                                  "run's vector would be taken); rename the token in one run or leave it out of the prompt")
@@ -164,6 +180,52 @@ def check_edit_args(args):
     except (OSError, ValueError) as e:
         raise SystemExit(f"inference.py: --init-image: {e}")
     return {"rgb": rgb, "mask": mask, "strength": strength, "auto": auto, "dilate": args.dilate or 0}
+
+
+def model_text_len(model_dir):
+    import json
+    cfg = os.path.join(model_dir, "text_encoder", "config.json")
+    if os.path.exists(cfg):
+        with open(cfg) as f:
+            return json.load(f).get("max_position_embeddings", 77)
+    return 77
+
+
+def check_region_args(args, run, edit):
+    """--region / --region-steps: every refusal, on the host, before any model is built.  -> None or {"regions": [regions.Region],
+    "steps": executed steps the regions act on, or None for all}"""
+    import json
+    from textboost_amd import regions as R
+    if not args.region:
+        if args.region_steps is not None:
+            raise SystemExit("inference.py: --region-steps needs --region \"WORDS=x0,y0,x1,y1\"")
+        return None
+    if args.attn_map is not None:
+        raise SystemExit("inference.py: --region does not go with --attn-map: the recorder recomputes an unmasked softmax from q and k, so it "
+                         "would report attention that did not happen under the regions; run --attn-map without --region")
+    try:
+        specs = [R.parse_region(r) for r in args.region]
+        with open(os.path.join(args.model, "unet", "config.json")) as f:
+            size = int(json.load(f).get("sample_size", 64))
+        from textboost_amd.attn_maps import run_tokenizer
+        regions = R.resolve_regions(run_tokenizer(args.model, run), args.prompt, model_text_len(args.model), specs, size, size)
+        steps = None
+        if args.region_steps is not None:
+            executed = args.steps
+            if edit is not None:
+                from textboost_amd.edit import strength_begin
+                executed = args.steps - strength_begin(args.steps, edit["strength"])
+            steps = R.steps_for(args.region_steps, executed)
+    except R.RegionError as e:
+        raise SystemExit(f"inference.py: {e}")
+    except OSError as e:
+        raise SystemExit(f"inference.py: --region: {e} (--model must be a local diffusers model directory)")
+    return {"regions": regions, "steps": steps}
+
+
+def regions_path(args):
+    stem = os.path.splitext(args.output)[0] if args.output is not None else args.prompt.replace(" ", "_")
+    return stem + "_regions.png"
 
 
 def check_auto_mask(pixel_mask, word):
@@ -236,6 +298,7 @@ def main(argv=None):
     if args.attn_map is not None:        # every refusal before anything reaches the device
         words, positions = attn_map_words(args.model, run, args.prompt, args.attn_map)
     edit = check_edit_args(args)
+    region = check_region_args(args, run, edit)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("inference.py needs an MI355X: the product path has no CPU fallback")
@@ -269,9 +332,13 @@ def main(argv=None):
         if words is not None:
             from textboost_amd.attn_maps import AttnMapRecorder
             recorder = AttnMapRecorder(pipe.unet)
+        rset = rsteps = None
+        if region is not None:
+            from textboost_amd import regions as R
+            rset, rsteps = R.RegionSet.for_unet(pipe.unet, region["regions"]), region["steps"]
         what = f"prompt {args.prompt!r}, seeds {args.seeds}"
         if edit is None:
-            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder)
+            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps)
         else:       # a seed's latent is the noise of its image; the photo is encoded once
             import numpy as np
             from textboost_amd import edit as E
@@ -288,7 +355,8 @@ def main(argv=None):
                 if not args.no_paste:
                     pixel_mask = torch.from_numpy(np.ascontiguousarray(pm)).to(pipe.dev)
             rgbx = pipe.edit_images(states[1], states[0], latents, z0, edit["strength"], latent_mask=latent_mask, pixel_mask=pixel_mask,
-                                    init_rgbx=init_rgbx if pixel_mask is not None else None, maps=recorder, what=what)
+                                    init_rgbx=init_rgbx if pixel_mask is not None else None, maps=recorder, what=what, regions=rset,
+                                    region_steps=rsteps)
         from PIL import Image
         images = [Image.fromarray(augment.to_host_rgb(rgbx[k])) for k in range(n)]
         word_maps = None
@@ -296,6 +364,11 @@ def main(argv=None):
             from textboost_amd.attn_maps import word_map
             token_maps = recorder.result()                                                  # [n, T, h, w]
             word_maps = torch.stack([word_map(token_maps, p) for p in positions], dim=1).cpu().numpy()     # [n, words, h, w]
+    if region is not None:
+        from textboost_amd import regions as R
+        R.preview(region["regions"], images[0].size).save(regions_path(args))
+        print(f"wrote {regions_path(args)}: " + "; ".join(f"{' '.join(r.words)} -> {int(r.cells.sum())} of {r.cells.size} latent cells, "
+                                                           f"token positions {list(r.positions)}" for r in region["regions"]))
     if args.output is not None:
         grid = Image.new("RGB", (n * images[0].width, images[0].height))     # diffusers.utils.make_image_grid(images, 1, n)
         for k, im in enumerate(images):

@@ -407,17 +407,17 @@ class Pipeline:
         """the UNet of one trained run: its K/V adapters folded in, or the base weights"""
         self.set_unet_adapters([(run.unet_lora, run.unet_rank, 1.0)] if run.unet_rank else [])
 
-    def images(self, cond, uncond, latents, what: str = "", maps=None) -> torch.Tensor:
+    def images(self, cond, uncond, latents, what: str = "", maps=None, regions=None, region_steps=None) -> torch.Tensor:
         """text states fp32 [B*T, D] twice, latents fp32 [B, 4, size, size] on the device -> int32 RGBX [B, 8 size, 8 size] (resident).
         Non-finite final latents raise before anything is decoded.  maps: an `attn_maps.AttnMapRecorder` of `self.unet` (the images do not
-        change with it)."""
-        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps)
+        change with it).  regions / region_steps: a `regions.RegionSet` of `self.unet` and how many steps it acts on (`HipSampler.denoise`)."""
+        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps, regions=regions, region_steps=region_steps)
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         return self.vae.decode_rgbx(x)
 
     def edit_images(self, cond, uncond, noise, z0, strength, latent_mask=None, pixel_mask=None, init_rgbx=None, maps=None,
-                    what: str = "") -> torch.Tensor:
+                    what: str = "", regions=None, region_steps=None) -> torch.Tensor:
         """`images` from an encoded photo (textboost_amd/edit.py; `HipSampler.denoise_from`): noise fp32 [B, 4, size, size] (a seed's latent is
         its image's noise), z0 fp32 [1, 4, size, size] shared by the B images, latent_mask uint8 [size, size] or None (non-zero = repaint).
         With pixel_mask (uint8 [8 size, 8 size]) and init_rgbx (the prepared photo, int32 RGBX [8 size, 8 size]) the decoded region is pasted
@@ -425,7 +425,7 @@ class Pipeline:
         from . import ops
         if (pixel_mask is None) != (init_rgbx is None):
             raise ValueError("the paste needs both pixel_mask and init_rgbx")
-        x = self.sampler.denoise_from(cond, uncond, z0, noise, strength, mask=latent_mask, maps=maps)
+        x = self.sampler.denoise_from(cond, uncond, z0, noise, strength, mask=latent_mask, maps=maps, regions=regions, region_steps=region_steps)
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         rgbx = self.vae.decode_rgbx(x)

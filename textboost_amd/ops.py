@@ -490,6 +490,20 @@ def attn_token_maps(q, k, maps, B, H, Sq, Skv, hd, scale=None, b0=0, nb=None, w=
     return maps
 
 
+def attention_region_fwd(q, k, v, o, lse, B, H, Sq, Skv, hd, key_region, query_regions, scale=None):
+    """attention_fwd's layout and result for a short key sequence (Skv <= 128) with the mask of regional prompting (csrc/region_attn.hip):
+    key j of batch row b is visible to query s only if key_region[b, j] < 0 or bit key_region[b, j] of query_regions[s] is set.
+    key_region int32 [B, Skv], query_regions uint32 [Sq] (stored as int32: torch has no arithmetic on uint32), both contiguous on the device."""
+    assert key_region.dtype == torch.int32 and key_region.is_contiguous() and key_region.numel() == B * Skv, (key_region.dtype, tuple(key_region.shape))
+    assert query_regions.dtype in (torch.int32, torch.uint32) and query_regions.is_contiguous() and query_regions.numel() == Sq, \
+        (query_regions.dtype, tuple(query_regions.shape), Sq)
+    assert q.stride(1) == 1 and k.stride(1) == 1 and v.stride(1) == 1 and o.stride(1) == 1
+    d = _attn_desc(q, k, v, o, lse, B, H, Sq, Skv, hd, scale if scale is not None else hd ** -0.5, False)
+    with _rec("attn_region_fwd_kernel", 4.0 * B * H * Sq * Skv * hd):
+        _launch("tb_attention_region_fwd", d, _dt(q), L.ptr(key_region), L.ptr(query_regions))
+    return o
+
+
 # ------------------------------------------------------------------ small streaming kernels
 def add_noise(x0, noise, timesteps, acp, noisy, velocity=None):
     B = x0.shape[0]

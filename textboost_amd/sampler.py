@@ -180,11 +180,14 @@ class HipSampler:
         self.t_dev = [torch.full((2 * B,), t, dtype=torch.int64, device=dev) for t in self.timesteps]
         self.generator: Optional[torch.Generator] = None
 
-    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None):
+    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None):
         """cond / uncond: fp16 or fp32 [B*77, D] text-encoder outputs.  Returns the final latents fp32 [B,4,h,w].
         step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`.
-        maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step."""
+        maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step.
+        regions: a `regions.RegionSet` of this UNet; the first `region_steps` executed steps (default: all) run the region-masked
+        cross-attention, the others the plain one."""
         B, sch = self.B, self.sch
+        region_steps = self._region_steps(regions, region_steps, self.steps)
         if maps is not None:
             maps.zero()
         if latents is None:
@@ -196,7 +199,7 @@ class HipSampler:
         ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
         n = self.x[0].numel()
         for i in range(self.steps):
-            eps2 = self._unet_forward(i, ehs, maps)
+            eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None)
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i)
             if getattr(sch, "needs_noise", False):  # the variance noise of the ancestral step rides in the m_prev operand
@@ -207,7 +210,7 @@ class HipSampler:
             ops.dpm_step(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc)
         return self.x
 
-    def denoise_from(self, cond_ehs, uncond_ehs, z0, noise, strength, mask=None, maps=None):
+    def denoise_from(self, cond_ehs, uncond_ehs, z0, noise, strength, mask=None, maps=None, regions=None, region_steps=None):
         """Image editing: diffusers' StableDiffusionImg2ImgPipeline and, with a mask, the latent blend of StableDiffusionInpaintPipeline for a
         4-channel UNet [3P restated: diffusers 0.29 is not installed here].  z0: the encoded image, fp32 [4, h, w] or [1, 4, h, w], shared by the B
         rows; noise: fp32 [B, 4, h, w], the noise of each row's image.  Steps begin .. steps-1 run, begin = `edit.strength_begin(steps, strength)`,
@@ -215,12 +218,14 @@ class HipSampler:
         `begin` is first order, as step 0 of `denoise` is.  mask: uint8 [h, w] on the device (non-zero = repaint), shared by channels and rows:
         after step i, x = mask ? x : alpha_{i+1} z0 + sigma_{i+1} noise in the step's own launch (`tb_dpm_step_blend`), so the kept cells end
         as z0 exactly.  Nothing of one call is kept for the next: the scheduler holds no step state, `begin` is an argument.
+        regions / region_steps: as in `denoise`, counted in EXECUTED steps (step `begin` is the first).
         Returns the final latents fp32 [B, 4, h, w]."""
         from .edit import strength_begin
         B, sch = self.B, self.sch
         if not isinstance(sch, DPMSolverPP2M):
             raise NotImplementedError(f"image editing runs on the DPM-Solver++ scheduler only, not on {type(sch).__name__}")
         begin = strength_begin(self.steps, strength)
+        region_steps = self._region_steps(regions, region_steps, self.steps - begin)
         z0 = z0.reshape(self.x.shape[1:]).to(self.x.device, torch.float32).contiguous()
         noise = noise.to(self.x.device, torch.float32).contiguous()
         if tuple(noise.shape) != tuple(self.x.shape):
@@ -239,7 +244,7 @@ class HipSampler:
         ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
         n = self.x[0].numel()
         for i in range(begin, self.steps):
-            eps2 = self._unet_forward(i, ehs, maps)
+            eps2 = self._unet_forward(i, ehs, maps, regions if i - begin < region_steps else None)
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i, begin)
             if mask is None:
@@ -249,14 +254,33 @@ class HipSampler:
                 ops.dpm_step_blend(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc, z0, noise, mask, k_a, k_s)
         return self.x
 
-    def _unet_forward(self, i, ehs, maps):
-        if maps is None:
+    def _region_steps(self, regions, region_steps, executed):
+        """how many of the `executed` steps run with `regions`: all by default; ValueError outside 1 .. executed or without regions"""
+        if regions is None:
+            if region_steps is not None:
+                raise ValueError("region_steps without regions")
+            return 0
+        if regions.B2 != self.unet.B or regions.T != self.unet.T or (regions.h, regions.w) != (self.unet.H, self.unet.W):
+            raise ValueError(f"the regions are built for batch {regions.B2}, {regions.T} tokens and a {regions.h} x {regions.w} grid; the UNet runs "
+                             f"batch {self.unet.B}, {self.unet.T} tokens, {self.unet.H} x {self.unet.W}")
+        if region_steps is None:
+            return executed
+        if not 1 <= int(region_steps) <= executed or int(region_steps) != region_steps:
+            raise ValueError(f"region_steps {region_steps}: a whole number of the {executed} executed steps, 1 .. {executed}")
+        return int(region_steps)
+
+    def _unet_forward(self, i, ehs, maps, regions=None):
+        if maps is None and regions is None:
             return self.unet.forward(self.x2, self.t_dev[i], ehs)
-        prev, self.unet.attn_maps = self.unet.attn_maps, maps
+        prev = self.unet.attn_maps, self.unet.regions
+        if maps is not None:
+            self.unet.attn_maps = maps
+        if regions is not None:
+            self.unet.regions = regions
         try:
             return self.unet.forward(self.x2, self.t_dev[i], ehs)
         finally:
-            self.unet.attn_maps = prev
+            self.unet.attn_maps, self.unet.regions = prev
 
     def sample(self, cond_ehs, uncond_ehs, latents=None):
         return self.vae.decode(self.denoise(cond_ehs, uncond_ehs, latents))

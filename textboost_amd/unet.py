@@ -140,6 +140,7 @@ class HipUNet:
         self.attn_fp8 = attn_fp8
         self._fp8_ws = None
         self.attn_maps = None   # an attn_maps.AttnMapRecorder: every cross-attention forward then also records its token maps (opt-in; None = no launch)
+        self.regions = None     # a regions.RegionSet: every cross-attention forward then runs the region-masked kernel with that level's table (opt-in; None = the plain forward)
         self.attn_loss = None   # enable_attn_loss(): the cross-attention localisation loss in the backward of the supervised layers (None = no launch)
         self._bufs: Dict[str, torch.Tensor] = {}
         self.tape: List = []
@@ -538,7 +539,10 @@ class HipUNet:
         k2, v2 = self.kv_all[:, ko:ko + C], self.kv_all[:, ko + C:ko + 2 * C]
         o2 = self.buf(prefix + ".o2", M, C)
         lse2 = self.buf(prefix + ".lse2", B * heads, HW, torch.float32)
-        ops.attention_fwd(q2, k2, v2, o2, lse2, B, heads, HW, T, hd)
+        if self.regions is None:
+            ops.attention_fwd(q2, k2, v2, o2, lse2, B, heads, HW, T, hd)
+        else:   # regional prompting (regions.py): restricted prompt tokens are visible inside their region only
+            ops.attention_region_fwd(q2, k2, v2, o2, lse2, B, heads, HW, T, hd, self.regions.key_region, self.regions.table(lvl_hw))
         if self.attn_maps is not None:
             self.attn_maps.record(q2, k2, heads, lvl_hw, hd)
         t2 = self.buf(prefix + ".t2", M, C)
