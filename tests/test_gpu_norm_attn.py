@@ -346,8 +346,17 @@ def test_attention_online_softmax_rescale_branch():
     o = torch.empty_like(q)
     lse = torch.empty(B, H, S, device="cuda")
     ops.attention_fwd(q, k, v, o, lse, B, H, S, S, hd)
-    oref, _ = ref_attention(q.float().view(B, S, C), k.float().view(B, S, C), v.float().view(B, S, C), H, False)
+    oref, lref = ref_attention(q.float().view(B, S, C), k.float().view(B, S, C), v.float().view(B, S, C), H, False)
     assert (o.float().view(B, S, C) - oref).abs().max().item() < 1e-2
+    # ... and at the O tolerances (rel-L2 / max-abs / worst channel) against the operand model of this kernel (tests/attn_peaked_ref.py: Q carries
+    # scale * log2 e, 64-key tiles with the 2^8 lazy re-base, P rounded before P.V, hd = 64 has no padding so the row sum is the fp32 one), + LSE
+    import attn_peaked_ref as R
+    q4, k4, v4 = [t.view(B, S, H, hd).transpose(1, 2) for t in (q, k, v)]
+    mod = R.model64(q4, k4, v4, torch.zeros_like(q4), rnd=torch.float16, scaled_fwd="q", tile=64, rowsum_of="exact")
+    parity("re-base branch O vs model", o.view(B, S, C), mod["O"].transpose(1, 2).reshape(B, S, C), rel=2e-3, maxabs=4e-3, ch_dim=2, ch_rel=3e-3)
+    parity("re-base branch O", o.view(B, S, C), oref, rel=2e-3, maxabs=4e-3, ch_dim=2, ch_rel=3e-3)
+    assert ((lse - mod["LSE"]).abs() / mod["LSE"].abs().clamp_min(1.0)).max().item() < 2e-3
+    assert ((lse - lref).abs() / lref.abs().clamp_min(1.0)).max().item() < 2e-3
 
 
 @pytest.mark.parametrize("B,H,Sq,Skv,hd", [(1, 2, 128, 64, 40), (1, 2, 128, 128, 40), (2, 3, 256, 192, 40), (1, 8, 1024, 1024, 40),
