@@ -1,5 +1,5 @@
 """hd = 40 self-attention backward at the metric shape: 80-byte (no pad chunk) vs 96-byte LDS rows.  The dQ kernel switches at run time
-(tb_attention_set_variant bit 8192 = padded rows); the dK/dV kernel is a build option (TB_LIB_SUFFIX=_alt TB_CFLAGS=-DTB_IL_DKV_PAD=1)."""
+(tb_attention_set_variant bit 8192 = padded rows); the dK/dV kernel's padded layout of round 3 is removed."""
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from textboost_amd import ops, _lib as L
@@ -31,7 +31,3 @@ L.lib().tb_attention_set_variant(base)
 for n, v_ in res.items(): print(f"[{os.environ.get('TB_LIB_SUFFIX', 'default lib')}] {n:18s} bwd (dq + dkv) median {sorted(v_)[1]:8.1f} us  min {min(v_):8.1f}")
 a, b_ = outs["dq 80-byte rows"], outs["dq 96-byte rows"]
 print("dq bit-equal:", torch.equal(a[:, :C], b_[:, :C]), " finite:", bool(torch.isfinite(a.float()).all()))
-torch.save(a.cpu(), f"/tmp/attn_bwd_out{os.environ.get('TB_LIB_SUFFIX', '')}.pt")
-if os.path.exists("/tmp/attn_bwd_out.pt") and os.path.exists("/tmp/attn_bwd_out_alt.pt"):
-    x, y = torch.load("/tmp/attn_bwd_out.pt"), torch.load("/tmp/attn_bwd_out_alt.pt")
-    print("dkv 80-byte vs 96-byte build bit-equal:", torch.equal(x, y))

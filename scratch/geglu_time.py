@@ -1,4 +1,4 @@
-"""GEGLU projection / GEGLU-backward launches at the 32x32 and 16x16 maps and the 128x320 Linear tile, library by TB_LIB_SUFFIX (round 5 DMAC2 A/B)"""
+"""GEGLU projection / GEGLU-backward launches at the 32x32 and 16x16 maps and the 128x320 Linear tile, library by TB_LIB_SUFFIX (written for the round 5 DMAC2 A/B: neutral, that variant is removed)"""
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from textboost_amd import ops, _lib as L

@@ -45,6 +45,25 @@ def test_library_exports_every_symbol_in_header():
     assert names == set(_lib._SIGS.keys()), names ^ set(_lib._SIGS.keys())
 
 
+def test_kernel_sources_keep_only_the_product_and_profiling_build_switches():
+    # a settled A/B switch is deleted, not parked behind the preprocessor: the bfloat16 product build and the time-stamp profiling builds are the only
+    # conditional compilation in the kernel sources
+    allowed = {"TB_BF16", "G8_PROF", "G8_PSTAMP", "CH_PROF", "FF_PROF", "TB_ATTN_PROF", "TB_IL_PROF"}
+    csrc = os.path.join(ROOT, "textboost_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(files) >= 10
+    seen = set()
+    for f in files:
+        for ln, line in enumerate(open(os.path.join(csrc, f)).read().splitlines(), 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            names = set(re.findall(r"[A-Za-z_]\w*", re.sub(r"//.*|/\*.*?\*/", "", m.group(2)))) - {"defined"}
+            assert names and names <= allowed, f"{f}:{ln}: {line.strip()}"
+            seen |= names
+    assert seen == allowed, allowed - seen
+
+
 def test_half_kind_switch_selects_the_library_and_the_dtype():
     from textboost_amd import _lib
     assert _lib.half_kind() == "fp16" and _lib.half_dtype() == torch.float16

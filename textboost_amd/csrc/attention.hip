@@ -21,7 +21,6 @@
 //     and dP arrives as dP - delta: no per-score fma / subtract;
 //   * the forward row sum l is an extra all-ones row of V^T in the head-dim padding (hd < 32*DT): O^T row hd accumulates sum_k P;
 //   * the softmax scale of dS is applied once to the dQ / dK accumulators at write-out (as FlashAttention-2 does).
-#define TB_ATTN_FUSED_DELTA 1  // A/B on MI355X: delta = rowsum(dO*O) inside the dQ kernel, +1.0 % steps/s vs its own launch
 #include "common.h"
 #include "../../include/textboost_hip.h"
 #include "attn_il.h"
@@ -35,10 +34,7 @@ constexpr int TLD = KVT + 4; // row stride (halfs) of transposed tiles: 136 B ->
 // 4 words (TSK halfs): stores and reads are both conflict-free, and on the read side the skew is part of the lane's base address / the
 // compile-time row-block offset -- no extra register or VALU op in the MFMA loops (an XOR swizzle made the forward kernel spill: +30 %).
 // PMC before: SQ_LDS_BANK_CONFLICT = 192 cycles per K/V tile = 28 % of the forward kernel's LDS-active cycles.
-#ifndef TB_ATTN_TRSKEW
-#define TB_ATTN_TRSKEW 1
-#endif
-constexpr int TSK = TB_ATTN_TRSKEW ? 8 : 0;
+constexpr int TSK = 8;
 __device__ __forceinline__ int tr_row(int d) { return d * TLD + (d >> 4) * TSK; }  // offset (halfs) of row d of a transposed tile
 constexpr float LOG2E = 1.4426950408889634f;
 __device__ __attribute__((aligned(16))) const f16 g_zero8[8] = {};  // out-of-range lanes load this line: no divergent branches
@@ -209,11 +205,6 @@ __device__ __forceinline__ void load_row_frags(f16x8* f, const f16* g, int64_t l
   }
 }
 
-#ifdef TB_ATTN_PRIO
-#define TB_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define TB_PRIO(x)
-#endif
 #define ZERO16(x)                \
   _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (x)[r_] = 0.f;
 #define FILL16(x, v)             \
@@ -230,24 +221,14 @@ __device__ __forceinline__ void scale_frags(f16x8* f, float c) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-#ifndef TB_ATTN_FOLDM
-#define TB_ATTN_FOLDM 1
-#endif
-#ifndef TB_ATTN_REBASE
-#define TB_ATTN_REBASE 8.f
-#endif
-#ifdef TB_FWD_OCC2
-#define TB_FWD_OCC3 0
-#else
-#define TB_FWD_OCC3 1
-#endif
+constexpr float REBASE = 8.f;  // lazy re-base threshold of the running maximum, in the log2 domain: see the forward kernel's softmax
 // FOLDM (hd a multiple of 8 with hd < 16 KS, i.e. SD1.x's hd = 40): the running max enters the score product through the head-dim PADDING --
 // K's padding column hd is all ones in LDS and the lane-owned Q fragment carries -m (rounded to fp16, and m is kept fp16-representable so l, the
 // re-base factor and the stored LSE all use exactly the value that was subtracted) in that slot -- so the score accumulators start from the
 // inline constant 0: no 16-register -m tuple (the 168-VGPR kernel spilled with it) and no 32 accumulator-init moves per tile (PMC: 32 of the
 // ~115 non-MFMA VALU ops per wave-tile).
 template <int DT, int KS, bool ONES, bool FOLDM>
-__global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 && TB_FWD_OCC3 ? 3 : (DT <= 4 ? 2 : 1))) void attn_fwd_kernel(const tb_attn_desc p, int remap) {  // 3 blocks/CU only where 168 VGPRs hold without spills
+__global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 ? 3 : (DT <= 4 ? 2 : 1))) void attn_fwd_kernel(const tb_attn_desc p, int remap) {  // 3 blocks/CU only where 168 VGPRs hold without spills
   constexpr int WD = DT * 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   f16* Ks = reinterpret_cast<f16*>(smem_raw);
@@ -317,7 +298,6 @@ __global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 && TB_FWD_OCC3 ? 3 : (DT <
       __syncthreads();
     }
     f32x16 s[2];
-    TB_PRIO(1);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       if (FOLDM) {
@@ -329,7 +309,6 @@ __global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 && TB_FWD_OCC3 ? 3 : (DT <
       for (int j = 0; j < KS; ++j)
         s[kt] = TB_MFMA_32x32x16(frag_rm<WD>(Ks, kt * 32 + l31, 2 * j + hi), qf[j], s[kt]);
     }
-    TB_PRIO(0);
     // masking is needed only on the ragged last tile / the causal diagonal: wave-uniform test keeps it off the common path
     const bool need_mask = (kv0 + KVT > p.Skv) || (p.causal && kv0 + KVT - 1 > qblk + wave * 32);
     if (need_mask) {
@@ -355,7 +334,7 @@ __global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 && TB_FWD_OCC3 ? 3 : (DT <
     // accumulators and well inside fp16 for the P operand; l and the stored LSE use the same m).  With "any excess > 0" 67 % of the L0 tiles
     // re-based (one of a wave's 32 rows sees a new maximum with probability ~ 1 - (1 - 1/t)^32 at tile t): ~70 VALU ops each (PMC:
     // SQ_INSTS_VALU_MUL_F32 / ADD_F32 ~ 11 per wave-tile).
-    if (first || __any(mx > TB_ATTN_REBASE)) {
+    if (first || __any(mx > REBASE)) {
       float d = first ? mx : fmaxf(mx, 0.f);
       if (FOLDM) d = (float)(f16)(m + d) - m;  // keep m fp16-representable: the Q slot subtracts exactly m (the difference is exact in fp32)
       if (!first) {
@@ -387,7 +366,6 @@ __global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 && TB_FWD_OCC3 ? 3 : (DT <
         s[kt][r] = pv;
         if (!ONES) l += pv;
       }
-    TB_PRIO(1);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -397,7 +375,6 @@ __global__ __launch_bounds__(256, (DT <= 2 && KS <= 3 && TB_FWD_OCC3 ? 3 : (DT <
         for (int d = 0; d < DT; ++d)
           o[d] = TB_MFMA_32x32x16(frag_tr(Vt, d, l31, kt * 32 + 16 * jj, hi), pf, o[d]);
       }
-    TB_PRIO(0);
     if (PF) {
       __syncthreads();
       cur ^= 1;
@@ -798,7 +775,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const tb_attn_desc
       }
       float mx = max3f(mx0, mx1, fmaxf(s[g][0][15], s[g][1][15]));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      if (first || __any(mx > TB_ATTN_REBASE)) {
+      if (first || __any(mx > REBASE)) {
         float d = first ? mx : fmaxf(mx, 0.f);
         if (FOLDM) d = (float)(f16)(m[g] + d) - m[g];
         if (!first) {
@@ -921,17 +898,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dma_kernel(const tb_attn_desc
 // lane-owned Q / dO fragments -- it only has to be FINITE: the next row's first chunk, or for the last row of the V tile the zeroed 64-byte slack
 // behind the stage.  80-byte rows put the 16 rows of a ds_read_b128 lane group on 16 distinct 16-byte bank slots (the 96-byte rows were a
 // 2-way conflict on every such read: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.50, profiles/r03_pmc_sq.txt) and the DMA moves 1/6 fewer bytes.
-#ifndef TB_DQ_ASMDMA
-#define TB_DQ_ASMDMA 0   // attn_bwd_dq_dma_kernel: 1 = the next tile's global -> LDS pieces go out as asm statements BETWEEN the tile's MFMAs (round 5 experiment:
-                         // 913 -> 911 us for the 64x64-map backward pair, 110.6 = 110.6 us at 32x32 -- neutral, the kernel is not piece-issue bound); 0 = the
-                         // builtin pieces in front of the tile's compute
-#endif
-// one global -> LDS piece (64 x 16 bytes, destination = wave-uniform LDS byte address + 16 lane) as an asm statement: may sit between MFMAs, where
-// the builtin gets a vmcnt(0) and a VGPR round trip of M0 in front (csrc/gemm_epi.h glds16_asm)
-__device__ __forceinline__ void attn_glds16_asm(const void* src, uint32_t lds_byte_addr) {
-  const uint32_t m = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(m), "v"(src) : "memory", "m0");
-}
+// (Round 5 tried the next tile's global -> LDS pieces as asm statements BETWEEN the tile's MFMAs instead of the builtin pieces in front of the tile's
+// compute: 913 -> 911 us for the 64x64-map backward pair, 110.6 = 110.6 us at 32x32 -- neutral, the kernel is not piece-issue bound; removed.)
 template <int DT, int KS, int PC, int NST, bool PAD = true>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const tb_attn_desc p, int remap, int publish) {
   constexpr int PCB = PC * 16, TILE_B = KVT * PCB;
@@ -1037,17 +1005,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const tb_attn_d
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const bool ld_on = t + NST - 1 < ntiles;
-    if (!TB_DQ_ASMDMA && ld_on) stage_loads(t + NST - 1, lslot);
-    // TB_DQ_ASMDMA: piece i of the next stage behind MFMA group i of this tile (three groups: scores of the first half, its dQ products, scores of the second half)
-    auto piece = [&](int i) {
-      const int tt = wave + 4 * i;
-      if (TB_DQ_ASMDMA && i < WI && ld_on && tt < NI && g_on[i]) {
-        const char* src = (tt >= PC ? Vg + (int64_t)(t + NST - 1) * KVT * ldv * 2 : Kg + (int64_t)(t + NST - 1) * KVT * ldk * 2) + g_off[i];
-        __builtin_amdgcn_sched_barrier(0);
-        attn_glds16_asm(src, lds0 + lslot * STAGE_B + tt * 1024);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
+    if (ld_on) stage_loads(t + NST - 1, lslot);
     const unsigned char* Ks = smem_raw + slot * STAGE_B;
     const uint32_t ka = lds0 + slot * STAGE_B + tr_lane;
 #pragma unroll
@@ -1060,7 +1018,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const tb_attn_d
         s = TB_MFMA_32x32x16(kfr, qf[j], s);
         dp = TB_MFMA_32x32x16(vfr, dof[j], dp);
       }
-      piece(kt == 0 ? 0 : 2);
       f16x4 ktf[2][DT][2];  // K^T fragments of this 32-key half: issued behind the score products, they arrive under the exponentials
       __builtin_amdgcn_sched_barrier(0);
 #define TB_TR(KT, JJ, D, HH) ktf[JJ][D][HH] = lds_tr_read_off<((KT) * 32 + 16 * (JJ) + 8 * (HH)) * PCB + (D) * 64>(ka);
@@ -1089,12 +1046,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const tb_attn_d
           dq[d] = TB_MFMA_32x32x16(a, dsf, dq[d]);
         }
       }
-      if (kt == 0) piece(1);
-    }
-    static_assert(!TB_DQ_ASMDMA || WI <= 3 || PAD, "three piece slots per tile");
-    if (WI > 3) {
-#pragma unroll
-      for (int i = 3; i < WI; ++i) piece(i);
     }
     slot = slot == NST - 1 ? 0 : slot + 1;
     lslot = lslot == NST - 1 ? 0 : lslot + 1;
@@ -1345,6 +1296,8 @@ __global__ __launch_bounds__(256) void attn_v8t_kernel(const tb_attn_desc p, int
 }
 
 // ------------------------------------------------------------------------------------------------ delta = rowsum(dO * O)
+// The stand-alone launch of the first version: nothing launches it since the dQ kernels compute delta themselves (A/B on MI355X: +1.0 % steps/s).
+// It is still compiled into the code object, which its removal would change.
 __global__ __launch_bounds__(256) void attn_delta_kernel(const tb_attn_desc p) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over B*Sq*H
   const int64_t total = (int64_t)p.B * p.Sq * p.H;
@@ -1364,11 +1317,9 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const tb_attn_desc p) {
 }
 
 // ------------------------------------------------------------------------------------------------ dQ
-#ifndef TB_DQ_OCC
-#define TB_DQ_OCC 2
-#endif
+constexpr int DQ_OCC = 2;  // workgroups per CU the narrow-head dQ kernel is compiled for
 template <int DT, int KS>
-__global__ __launch_bounds__(256, (DT <= 2 ? TB_DQ_OCC : 1)) void attn_bwd_dq_kernel(const tb_attn_desc p, int remap, int publish) {
+__global__ __launch_bounds__(256, (DT <= 2 ? DQ_OCC : 1)) void attn_bwd_dq_kernel(const tb_attn_desc p, int remap, int publish) {
   constexpr int WD = DT * 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   f16* Ks = reinterpret_cast<f16*>(smem_raw);
@@ -1391,7 +1342,6 @@ __global__ __launch_bounds__(256, (DT <= 2 ? TB_DQ_OCC : 1)) void attn_bwd_dq_ke
   const bool qok = q < p.Sq;
   const int64_t sidx = ((int64_t)b * p.H + h) * p.Sq + (qok ? q : 0);
   const float lse2 = p.LSE[sidx] * LOG2E;
-#ifdef TB_ATTN_FUSED_DELTA
   float delta;  // rowsum(dO * O) computed here and published for the dK/dV kernel that runs next on the stream
   {
     const f16* Og = (const f16*)p.O + (int64_t)b * p.Sq * p.ldo + h * p.hd;
@@ -1412,9 +1362,6 @@ __global__ __launch_bounds__(256, (DT <= 2 ? TB_DQ_OCC : 1)) void attn_bwd_dq_ke
     p.ws[sidx] = -lse2;
     p.ws[(int64_t)p.B * p.H * p.Sq + sidx] = -delta;
   }
-#else
-  const float delta = p.Delta[sidx];
-#endif
   // FOLD: -lse and -delta enter the two products as accumulator inputs (S' = c q.k - lse is the exp2 argument, dP' = dO.v - delta);
   // costs 32 registers, so the wide-head instantiations (already AGPR-bound at one wave per SIMD) subtract explicitly instead
   constexpr bool FOLD = DT <= 2;
@@ -2205,7 +2152,7 @@ int launch_fwd(const tb_attn_desc& d, hipStream_t s) {
     TB_CHECK_LAUNCH();
     return TB_OK;
   }
-  if (TB_ATTN_FOLDM && DT <= 2 && d.hd < WD && d.hd < 16 * KS && d.hd % 8 == 0)  // padding in the head dim of BOTH products: see FOLDM
+  if (DT <= 2 && d.hd < WD && d.hd < 16 * KS && d.hd % 8 == 0)  // padding in the head dim of BOTH products: see FOLDM
     hipLaunchKernelGGL((attn_fwd_kernel<DT, KS, true, (DT <= 2)>), grid, dim3(256), lds, s, d, ((g_attn_dma >> 2) & 1) ^ 1);
   else if (d.hd < WD)  // head-dim padding exists: the row sum rides on the PV product (all-ones row hd of V^T)
     hipLaunchKernelGGL((attn_fwd_kernel<DT, KS, true, false>), grid, dim3(256), lds, s, d, ((g_attn_dma >> 2) & 1) ^ 1);
@@ -2256,12 +2203,6 @@ int launch_bwd(const tb_attn_desc& d, hipStream_t s) {
                         (DT == 3 && KS == 5 && d.hd == 80 && !(g_attn_dma & 512))) && !d.causal && d.Sq % KVT == 0 && d.Skv % 128 == 0 && !(g_attn_dma & 128) &&
                        d.ws && d.ws_floats >= 2 * (int64_t)d.B * d.H * d.Sq && (int64_t)(d.Skv / 128) * d.H * d.B >= 512 &&
                        d.ldq % 8 == 0 && d.lddo % 8 == 0 && (int64_t)KVT * (d.ldq > d.lddo ? d.ldq : d.lddo) * 2 < ((int64_t)1 << 31);
-#ifndef TB_ATTN_FUSED_DELTA
-  {
-    int64_t total = (int64_t)d.B * d.Sq * d.H;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d);
-  }
-#endif
   {
     size_t lds = (2 * RM<WD>::SIZE + TR<WD>::SIZE) * sizeof(f16);
     static bool attr_done = false;

@@ -19,9 +19,7 @@ namespace {
 
 constexpr int KVT = 64;
 constexpr float LOG2E = 1.4426950408889634f;
-#ifndef TB_IL_REBASE
-#define TB_IL_REBASE 8.f
-#endif
+constexpr float IL_REBASE = 8.f;  // lazy re-base threshold of the running maximum (log2 domain), as REBASE in attention.hip
 __device__ __attribute__((aligned(16))) const f16 g_zero8_il[8] = {};
 typedef const __attribute__((address_space(1))) f16x8* gvec8_t;
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -147,7 +145,7 @@ __device__ __forceinline__ void sm_slice(FwdGroup& g, SmTmp& t, bool first, bool
     // Lazy re-base (attention.hip attn_fwd_kernel): m only has to stay within 2^REBASE of the true row maximum; it stays fp16-representable so
     // that the Q slot subtracts exactly the m that l and the stored LSE use.
     const float mx = t.mx0;
-    if (first || __any(mx > TB_IL_REBASE)) {
+    if (first || __any(mx > IL_REBASE)) {
       float d = first ? mx : fmaxf(mx, 0.f);
       d = (float)(f16)(g.m + d) - g.m;
       if (!first) {
@@ -438,11 +436,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_il_kernel(const tb_attn_desc 
 // Rows of hd / 8 = 5 chunks WITHOUT a pad chunk (round 4; 80-byte pitch: the b128 row reads of a 16-lane group land on 16 distinct bank slots, the
 // 96-byte rows were a 2-way conflict).  The k-step that runs past a row's end multiplies the zeros of the lane-owned K / V fragments, so what it
 // reads only has to be finite: the next row, the dO tile behind the Q tile, and behind the dO tile a zeroed 64-byte gap in front of the statistics
-// rows (raw fp32 bit patterns: NOT safe to read as fp16).  TB_IL_DKV_PAD=1 builds the padded layout of round 3.
-#ifndef TB_IL_DKV_PAD
-#define TB_IL_DKV_PAD 0
-#endif
-constexpr int D_PC = TB_IL_DKV_PAD ? 6 : 5, D_PCB = D_PC * 16, D_TILE_B = KVT * D_PCB, D_GAP = 64, D_STAGE_B = 2 * D_TILE_B + D_GAP + 2 * KVT * 4 + 64,
+// rows (raw fp32 bit patterns: NOT safe to read as fp16).  (The padded 6-chunk layout of round 3 is removed.)
+constexpr int D_PC = 5, D_PCB = D_PC * 16, D_TILE_B = KVT * D_PCB, D_GAP = 64, D_STAGE_B = 2 * D_TILE_B + D_GAP + 2 * KVT * 4 + 64,
               D_NST = 4;
 
 struct DkvState {
@@ -588,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_il_kernel(const tb_attn_d
     const int tensor = t >= PC ? 1 : 0;
     const int f = (t - tensor * PC) * 64 + lane;
     const int row = f / PC, cc = f - row * PC;
-    g_on[i] = t < 2 * PC && (!TB_IL_DKV_PAD || cc < PC - 1);
+    g_on[i] = t < 2 * PC;   // (the removed padded layout also masked its pad chunk here; without the flag hipcc numbers the kernel's registers differently)
     g_off[i] = (uint32_t)((int64_t)row * (tensor ? lddo : ldq) * 2 + cc * 16);
   }
   int n_issued = 0;
@@ -610,13 +605,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_il_kernel(const tb_attn_d
       }
     }
   };
-  if (TB_IL_DKV_PAD) {
-    for (int u = threadIdx.x; u < 2 * KVT * D_NST; u += 256) {  // pad chunks of every row of every stage: zeros (finite)
-      const int s_ = u / (2 * KVT), r = u - s_ * 2 * KVT;
-      const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      *(f16x8*)(smem_raw + s_ * D_STAGE_B + (r >= KVT ? D_TILE_B : 0) + (r & (KVT - 1)) * D_PCB + (PC - 1) * 16) = z;
-    }
-  }
   if (threadIdx.x < D_NST * 4) {  // the gap between the dO tile and the statistics rows of every stage
     const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     *(f16x8*)(smem_raw + (threadIdx.x >> 2) * D_STAGE_B + 2 * D_TILE_B + (threadIdx.x & 3) * 16) = z;

@@ -442,12 +442,7 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
   int tile, slice;
   {
     const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-#ifdef TB_GEMM_NO_XCD
-    const int logical = bid;
-    (void)xcd; (void)q; (void)r;
-#else
     const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-#endif
     tile = logical / S;       // the S k-slices of one tile are adjacent (same XCD)
     slice = logical - tile * S;
   }
@@ -476,7 +471,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
 
   // ---- per-lane source descriptors (rows are fixed across k-tiles)
   const f16* a_ptr[AI];
-  const f16* a2_ptr[AI];
   bool a_ok[AI];
   int py[AI], px[AI], a_sw[AI], a_step[AI];
   int64_t pbase[AI];
@@ -487,10 +481,8 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
     a_ok[i] = m < p.M;
     const int64_t mm = a_ok[i] ? m : 0;
     a_sw[i] = (cp ^ SWZ(row)) * 8;  // source chunk (halfs) that belongs at LDS chunk position cp of this row
-    if (MODE == TB_A_LINEAR) {
-      a_ptr[i] = (const f16*)p.A + mm * p.lda + a_sw[i];
-      a2_ptr[i] = p.A2 ? (const f16*)p.A2 + mm * p.lda2 + a_sw[i] : nullptr;
-    } else if (p.transposed == 2) {
+    if (MODE == TB_A_LINEAR) continue;  // Linear rows are addressed by the 32-bit offsets below
+    if (p.transposed == 2) {
       // phase-ordered rows (see phase_q below): row m' = class * (M / 4) + ((b * Hout/2 + i) * Wout/2 + j)  ->  output pixel (2 i + qy, 2 j + qx)
       const int64_t mq = p.M >> 2;
       const int cls = (int)(mm / mq);
@@ -519,20 +511,11 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
   // only issues its class's taps: 2.25 taps per pixel on average instead of 9.  The epilogue maps tile rows back to map order.
   const int phase_q = (MODE == TB_A_CONV3X3 && p.transposed == 2) ? 3 - (int)(m0 / (p.M >> 2)) : -1;
   const int ph_nky = phase_q >= 0 && (phase_q >> 1) ? 2 : 1, ph_nkx = phase_q >= 0 && (phase_q & 1) ? 2 : 1;
-  const f16* w_ptr[BI];
-  const f16* w2_ptr[BI];
+  // (w_ok is not read: the old pointer-per-row addressing that used it is removed.  It stays because dropping the comparison reorders a few
+  // prologue instructions, and the code object would no longer be byte-identical to the measured one.)
   bool w_ok[BI];
 #pragma unroll
-  for (int i = 0; i < BI; ++i) {
-    const int row = wave * (BN / 4) + i * RPI + rl;
-    const int64_t n = n0 + row;
-    w_ok[i] = n < p.N;
-    const int64_t nn = w_ok[i] ? n : 0;
-    const int sw = (cp ^ SWZ(row)) * 8;
-    w_ptr[i] = (const f16*)p.W + nn * p.ldw + sw;
-    w2_ptr[i] = p.W2 ? (const f16*)p.W2 + nn * p.ldw2 + sw : nullptr;
-  }
-#ifndef TB_GEMM_OLD_ADDR
+  for (int i = 0; i < BI; ++i) w_ok[i] = n0 + wave * (BN / 4) + i * RPI + rl < p.N;
   // Fast addressing (operands below 4 GiB, checked by the host): every lane keeps a 32-bit byte offset from the operand base and the
   // k advance lives in the uniform base, so a k-tile's loads cost no vector ALU work at all (plain VALU does not overlap the MFMAs of
   // the co-resident waves).  Rows past M / N are clamped to the last row instead of the zero line: they only
@@ -553,7 +536,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
     w_off[i] = (uint32_t)((nn * p.ldw + sw) * 2);
     w2_off[i] = (uint32_t)((nn * p.ldw2 + sw) * 2);
   }
-#endif
 
   const int kpt = (MODE == TB_A_CONV3X3) ? p.Cin / BK : 1;  // k-tiles per tap
   const int nk_all = phase_q >= 0 ? ph_nky * ph_nkx * kpt : (int)(p.K / BK);
@@ -569,13 +551,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
     if (MODE == TB_A_LINEAR) {
       const bool second = kt >= nk1;  // wave-uniform: which K-source this k-tile comes from
       const int koff = (second ? kt - nk1 : kt) * BK;
-#ifdef TB_GEMM_OLD_ADDR
-#pragma unroll
-      for (int i = 0; i < AI; ++i) {
-        const f16* src = a_ok[i] ? (second ? a2_ptr[i] : a_ptr[i]) + koff : zero;
-        glds16(src, As + i * RPI * BK);
-      }
-#else
       if (second) {
         const char* base = (const char*)p.A2 + (int64_t)koff * 2;
 #pragma unroll
@@ -585,7 +560,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
 #pragma unroll
         for (int i = 0; i < AI; ++i) glds16((const f16*)(base + a_off[i]), As + i * RPI * BK);
       }
-#endif
     } else {
       const int tap = kt / kpt;   // (phase mode: index into the class's tap list)
       const int cc = kt - tap * kpt;
@@ -634,13 +608,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
         const int ky = ph_nky == 2 ? 2 * ty_ : 1, kx = ph_nkx == 2 ? 2 * tx_ : 1;
         koff = ((ky * 3 + kx) * kpt + cc) * BK;
       }
-#ifdef TB_GEMM_OLD_ADDR
-#pragma unroll
-      for (int i = 0; i < BI; ++i) {
-        const f16* src = w_ok[i] ? (second ? w2_ptr[i] : w_ptr[i]) + koff : zero;
-        glds16(src, Bs + i * RPI * BK);
-      }
-#else
       if (second) {
         const char* base = (const char*)p.W2 + (int64_t)koff * 2;
 #pragma unroll
@@ -650,7 +617,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
 #pragma unroll
         for (int i = 0; i < BI; ++i) glds16((const f16*)(base + w_off[i]), Bs + i * RPI * BK);
       }
-#endif
     }
   };
 
@@ -667,30 +633,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
   auto compute = [&](int buf) {
     const f16* Ab = smem + buf * STAGE + (wm * WTM) * BK;
     const f16* Bb = smem + buf * STAGE + A_TILE + (wn * WTN) * BK;
-#ifdef TB_GEMM_OLD_ADDR
-#pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) {
-      f16x8 af[TM], bf[TN];
-      const int ch = kk * 2 + hi;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = i * 32 + l31;
-        af[i] = *(const f16x8*)(Ab + row * BK + ((ch ^ SWZ(row)) << 3));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = j * 32 + l31;
-        bf[j] = *(const f16x8*)(Bb + row * BK + ((ch ^ SWZ(row)) << 3));
-      }
-      __builtin_amdgcn_s_setprio(1);  // +0.2..0.5 % in situ: MFMA bursts win arbitration over the co-resident block's loads
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)  // transposed accumulator: rows = n (from W), cols = m (from A)
-          acc[i][j] = TB_MFMA_32x32x16(bf[j], af[i], acc[i][j]);
-      __builtin_amdgcn_s_setprio(0);
-    }
-#else
     // all fragment reads of the k-tile are issued before its first MFMA (one exposed LDS latency per k-tile instead of one per 16-wide
     // k-step; s_setprio inside the loop had been a scheduling barrier that kept the compiler from doing this itself)
     constexpr int NKK = BK / 16;
@@ -716,7 +658,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 3 : (NST >= 4 && BM == 128 ? 1 : 
 #pragma unroll
         for (int j = 0; j < TN; ++j)  // transposed accumulator: rows = n (from W), cols = m (from A)
           acc[i][j] = TB_MFMA_32x32x16(bf[kk][j], af[kk][i], acc[i][j]);
-#endif
   };
   if constexpr (NST == 2) {
     stage(0, 0);
@@ -1134,10 +1075,6 @@ int dispatch_tile(const tb_gemm_desc& d, hipStream_t s) {
   // exposed latency (prologue, per-k-tile drain, residual loads), not by MFMA rate (scratch/tiles.py, one MI355X: 8192x640x640
   // 26.2 -> 21.3 us, 2048x5120x1280 78 -> 57 us, 32768x1280x320 115 -> 95 us; 2048x3840x1280 (480 tiles = one round) 39.8 vs 46.8;
   // halo conv 640->640 @32x32 94.5 -> 81.5 us, 1280->640 168 -> 151 us)
-#ifdef TB_NO_NARROW
-  bool narrow = false;
-  const bool by_rule = false;
-#else
   const bool odd64 = (d.N % 128) != 0 && (d.N % 128) <= 64;
   bool narrow = odd64;
   if ((MODE == TB_A_LINEAR || !(g_conv_narrow & 2)) && g_force_tile != 4) {
@@ -1145,7 +1082,6 @@ int dispatch_tile(const tb_gemm_desc& d, hipStream_t s) {
     if (b128 >= 256 && !(b128 >= 384 && b128 <= 512)) narrow = true;
   }
   const bool by_rule = narrow && !odd64;  // such grids are never small enough for the 64x64 fallback below
-#endif
   const int64_t blocks = ((d.M + 127) / 128) * ((d.N + (narrow ? 63 : 127)) / (narrow ? 64 : 128));
   if (MODE == TB_A_CONV3X3 && g_halo && d.stride == 1 && !d.upsample && !d.transposed && !d.shift && d.Hin == d.Hout && d.Win == d.Wout &&
       halo_wshift(d.Wout, d.Hout) > 0 && ((int64_t)d.Hout * d.Wout >= 128 ? (g_halo & 1) : ((g_halo & 2) && d.M % 128 == 0))) {
@@ -1198,12 +1134,10 @@ int dispatch_tile(const tb_gemm_desc& d, hipStream_t s) {
       if (b64 >= 224 && b64 <= 512) return launch<64, 64, MODE>(d, s);
     }
   }
-#ifndef TB_SMALL_TILE_BLOCKS
-#define TB_SMALL_TILE_BLOCKS 320  // A/B on one MI355X: 96 -1.6 %, 192 base, 320 +1.0 %, 512 -1.0 % steps/s
-#endif
+  constexpr int64_t SMALL_TILE_BLOCKS = 320;  // A/B on one MI355X: 96 -1.6 %, 192 base, 320 +1.0 %, 512 -1.0 % steps/s
   if (g_force_tile && g_force_tile < 4 && S == 1)
     return g_force_tile == 1 ? launch<64, 64, MODE>(d, s) : (g_force_tile == 2 ? launch<128, 64, MODE>(d, s) : launch<128, 128, MODE>(d, s));
-  if (S == 1 && !by_rule && blocks < TB_SMALL_TILE_BLOCKS) return launch<64, 64, MODE>(d, s);  // small problems without workspace: smaller tiles
+  if (S == 1 && !by_rule && blocks < SMALL_TILE_BLOCKS) return launch<64, 64, MODE>(d, s);  // small problems without workspace: smaller tiles
   return narrow ? launch<128, 64, MODE>(d, s, S) : launch<128, 128, MODE>(d, s, S);
 }
 

@@ -19,31 +19,8 @@
 #ifndef G8_PROF
 #define G8_PROF 0  // profiling build: per-phase s_memtime sums of waves 0 and 4 of workgroup 0 into dbg[16..]
 #endif
-#ifndef G8_DMAC
-#define G8_DMAC 9  // bit 3: DMACH (the 256 x 80 convolution tile on a 4-slot ring), bit 0: DMAC, bit 1: DMACC (measured SLOWER, off), bit 2: DMAC2 (measured neutral, off); A/B build switch (TB_CFLAGS=-DG8_DMAC=n) (TB_CFLAGS=-DG8_DMAC=0): the Linear tiles' global -> LDS pieces in the LOAD phase, as in round 4
-#endif
-#ifndef G8_DMACC_MASK
-#define G8_DMACC_MASK 0xA  // DMACC: bit k = load slot k of a convolution step goes out in the COMPUTE phase of its half (slots 0 .. WI - 1 weight pieces, WI the halo piece)
-#endif
-#ifndef G8_DMAC_L
-#define G8_DMAC_L 0  // DMAC tiles: load slots of a step that stay in the LOAD phase (experiment: balancing the two phases of the 128 x 160 tile)
-#endif
 #ifndef G8_PSTAMP
 #define G8_PSTAMP 0  // profiling build: extra prologue stamps in dbg[3] (setup done), dbg[4] (prologue stages issued), dbg[5] (their wait done)
-#endif
-#ifndef G8_NT
-#define G8_NT 0  // experiment (TB_CFLAGS=-DG8_NT=1): non-temporal stores in the lean / GEGLU epilogues
-#endif
-#if G8_NT
-#define G8_ST(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define G8_ST(ptr, val) (*(ptr) = (val))
-#endif
-#ifndef G8_STREAM
-#define G8_STREAM 1  // the 256 x 160 / 256 x 128 convolution tiles (MT >= 4, 3-slot weight ring) as ONE instruction stream per wave: the fragments of the next 32-wide k-step are read between the MFMAs of this one, one barrier per tap (0: the round-2 LOAD / COMPUTE phases of two barrier-shifted wave groups)
-#endif
-#ifndef G8_ABL
-#define G8_ABL 0  // profiling builds (TB_CFLAGS=-DG8_ABL=bits): 1 = no MFMAs, 2 = no in-loop global->LDS loads, 4 = no fragment reads
 #endif
 
 namespace {
@@ -315,8 +292,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
   G8_STAMP(7)
 #endif
   const int cp = lane & 7, rl = lane >> 3;
-  // STREAM: see the main loop
-  constexpr bool STREAM = G8_STREAM && ST && CONV && SUB == 0 && MT >= 4 && NT <= 5 && NS == 3 && KH == 1 && !G8_PROF;
+  // STREAM: the 256 x 160 / 256 x 128 convolution tiles (MT >= 4, 3-slot weight ring) as ONE instruction stream per wave, see the main loop (the other
+  // tiles keep the round-2 LOAD / COMPUTE phases of two barrier-shifted wave groups)
+  constexpr bool STREAM = ST && CONV && SUB == 0 && MT >= 4 && NT <= 5 && NS == 3 && KH == 1 && !G8_PROF;
   // ---- A-panel sources of this lane (fixed across chunks, + 64 halfs per chunk)
   const f16* h_ptr[MAXHI];
   int h_step[MAXHI];
@@ -398,7 +376,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
   // step t is always (t / 3, t % 3)
   const int wtap0 = p.sign > 0 ? 0 : TAPS - 1, wtapd = p.sign > 0 ? 1 : -1;
   auto issue_slot = [&](int k, int lc, int ltap, int lslot, int c, int tap, int lnext) {  // lnext: the loaded stage belongs to chunk c + 1
-    if (G8_ABL & 2) return;
     if (k < WI) {
       const int j = wave + 8 * k;
       if (lc < nchunk && j < NI_W) {
@@ -434,34 +411,27 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
     return n;
   };
   // DMAC (round 5; Linear tiles whose step is one phase pair, rings of >= 4 stages): the step's global -> LDS pieces are issued in the COMPUTE phase,
-  // between the MFMAs, not in the LOAD phase.  Measured on the 128 x 80 tile (scratch/kh_time.py with -DG8_ABL builds): a k-step took 0.625 us =
+  // between the MFMAs, not in the LOAD phase.  Measured on the 128 x 80 tile (scratch/kh_time.py on ablation builds -- no MFMAs / no in-loop loads /
+  // no fragment reads -- since removed): a k-step took 0.625 us =
   // 0.26 (MFMAs + the two barriers) + 0.10 .. 0.17 (fragment reads) + 0.20 (the pieces) -- the phases ADDED: a LOAD phase carrying 12 fragment reads and
   // 3.25 pieces per wave ran ~600 cycles beside a COMPUTE phase of 160, and a piece costs 100 .. 185 issue cycles inside such a phase against ~60 among
   // bare MFMAs (microarch guide).  The counted wait stays at the end of the LOAD phase (so the second wave group's pieces have landed one interval
   // before the first group reads them): what must have landed is the next step's stage, issued two steps ago; the previous step's pieces stay in flight.
-  constexpr bool DMAC = G8_DMAC && !CONV && MT < 4 && NS >= 4 && !(G8_ABL & 2);
-  // DMACC: the same for the 9-tap convolution tiles whose step is TWO phase pairs (MT >= 4: 256 pixels x 160 / 128 channels, 3-slot weight ring): the
-  // pieces of a step go out in its two COMPUTE phases; at the end of the second LOAD phase everything but this step's first-half pieces has landed,
-  // i.e. the next step's weight stage (issued during the previous step) and every halo piece issued before this step
-  // (DMACC measured, one MI355X, scratch/g8_time.py: every piece in the COMPUTE phases (G8_DMACC_MASK = 0xF) 320 -> 320 @ 64x64 57.7 -> 65.5 us, 960 -> 320
-  // 171 -> 184 us, the step 28.9 -> 30.0 ms; one piece per half (0xA) 57.1 -> 55.7 / 166 -> 160 us but 29.12 = 29.15 ms in the step: the phase stamps
-  // (-DG8_PROF) say LOAD 527 cycles against COMPUTE 365 per half-step, and the LOAD phase is its 36 KB of fragment reads (288 cycles of LDS transfer at
-  // 128 B/clk), not the two pieces; off)
-  // DMAC2: Linear tiles with TWO phase pairs per step on a 2-stage ring (the 128 x 128 GEGLU tile, 128 x 320): all pieces of the next stage go out in
-  // the FIRST compute phase; the wait for them stays at the end of the second LOAD phase (vmcnt(0)), one interval before the other wave group reads them
-  // (DMAC2 measured, scratch/geglu_time.py: GEGLU 8192x5120x640 126 -> 119..125 us, 32768x320x1280 46.7 -> 47.8 us, the step 29.00 = 29.00 ms: neutral; off)
-  constexpr bool DMAC2 = (G8_DMAC & 4) && !CONV && MT >= 4 && NS == 2 && !(G8_ABL & 2);
-  // DMACH (bit 3): the 256-pixel x 80-channel convolution tile (MT = 2: ONE phase pair per step) on a 4-slot weight ring, as DMAC: every piece of a step
+  constexpr bool DMAC = !CONV && MT < 4 && NS >= 4;
+  // (Round 5 also tried, and removed: keeping some of a DMAC step's slots in the LOAD phase to balance the two phases of the 128 x 160 tile; and
+  //  "DMACC", the same for the 9-tap convolution tiles whose step is TWO phase pairs (MT >= 4: 256 pixels x 160 / 128 channels, 3-slot weight ring), the
+  //  pieces of a step going out in its two COMPUTE phases.  Measured, one MI355X, scratch/g8_time.py: every piece in the COMPUTE phases 320 -> 320 @ 64x64
+  //  57.7 -> 65.5 us, 960 -> 320 171 -> 184 us, the step 28.9 -> 30.0 ms; one piece per half 57.1 -> 55.7 / 166 -> 160 us but 29.12 = 29.15 ms in the
+  //  step: the phase stamps (-DG8_PROF) said LOAD 527 cycles against COMPUTE 365 per half-step, and the LOAD phase is its 36 KB of fragment reads (288
+  //  cycles of LDS transfer at 128 B/clk), not the two pieces.  And "DMAC2", Linear tiles with TWO phase pairs per step on a 2-stage ring (the 128 x 128
+  //  GEGLU tile, 128 x 320), all pieces of the next stage going out in the FIRST compute phase: GEGLU 8192x5120x640 126 -> 119..125 us, 32768x320x1280
+  //  46.7 -> 47.8 us, the step 29.00 = 29.00 ms: neutral.  These tiles now run STREAM or the plain LOAD-phase issue.)
+  // DMACH: the 256-pixel x 80-channel convolution tile (MT = 2: ONE phase pair per step) on a 4-slot weight ring, as DMAC: every piece of a step
   // between the MFMAs of its COMPUTE phase, the wait at the end of the LOAD phase leaves the previous step's pieces in flight.  Phase stamps of the
   // 3-slot version (-DG8_PROF, 640 -> 640 @ 32x32): LOAD 709 cycles against 355 for the 20 MFMAs -- the imbalance DMAC removed from the Linear tiles.
-  constexpr bool DMACH = (G8_DMAC & 8) && CONV && SUB == 0 && MT < 4 && NS == 4 && !(G8_ABL & 2);
-  constexpr bool DMACC = (G8_DMAC & 2) && CONV && SUB == 0 && MT >= 4 && NS == 3 && !(G8_ABL & 2);
+  constexpr bool DMACH = CONV && SUB == 0 && MT < 4 && NS == 4;
   const uint32_t as_addr0 = lds_addr(As), ws_addr0 = lds_addr(Ws);
-  auto conv_slot_issues = [&](int k, int lc, int c, int tap) -> int {   // DMACC: does this wave issue a piece for slot k in step (c, tap)?
-    if (k < WI) return (lc < nchunk && wave + 8 * k < NI_W) ? 1 : 0;
-    return (tap < MAXHI && c + 1 < nchunk && wave + 8 * tap < NI_H) ? 1 : 0;
-  };
-  auto issue_conv_slot_asm = [&](int k, int lc, int ltap, int lslot, int c, int tap) {   // DMACC: issue_slot's SUB == 0 convolution case as asm pieces
+  auto issue_conv_slot_asm = [&](int k, int lc, int ltap, int lslot, int c, int tap) {   // DMACH: issue_slot's SUB == 0 convolution case as asm pieces
     if (k < WI) {
       const int j = wave + 8 * k;
       if (lc < nchunk && j < NI_W)
@@ -612,20 +582,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
         a0[i] = ab + (ar << 7) + ((lq ^ ((ar + shift) & 7)) << 4);
       }
     };
-    int abl_c = c_begin;
     uint32_t wb = bb0;   // weight-fragment base of the sub-step being read (slot and k-half folded in, set once per sub-step)
-    if (G8_ABL & 4) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j) asm volatile("" : "=v"(bf[s][j]));
-#pragma unroll
-        for (int i = 0; i < MT; ++i) asm volatile("" : "=v"(af[s][i]));
-      }
-    }
     auto read_frag = [&](int r, int s) {   // fragment read r of a sub-step: r < NT weights, then activations
-      if (G8_ABL & 4) return;
-      if ((G8_ABL & 64) && abl_c > c_begin) return;   // (as bit 32) fragment reads in the first chunk only
       if (r < NT) bf[s][r] = lds_read16_off<2048>(wb, r);
       else af[s][r - NT] = lds_read16(s ? (a0[r - NT] ^ 64) : a0[r - NT]);
     };
@@ -641,8 +599,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
     for (int k = 0; k < WI; ++k) wmask |= (wave + 8 * k < NI_W ? 1u : 0u) << k;
     hmask = __builtin_amdgcn_readfirstlane(hmask), wmask = __builtin_amdgcn_readfirstlane(wmask);
     auto issue_piece = [&](int q, int lc, int ltap, int lslot, int c, int tap) {   // q: 0 the halo piece, then weight pieces WI - 1 .. 0
-      if (G8_ABL & 2) return;
-      if ((G8_ABL & 32) && c > c_begin) return;   // (timing builds with REAL operand data: the matrix pipe's clock depends on it) pieces in the first chunk only
+      (void)c_begin;   // keeps c_begin in the closure, where the removed first-chunk-only timing builds had it: without the capture hipcc numbers this
+                       // kernel's registers differently (same instructions), and the code object would no longer be byte-identical to the measured one
       if (q == 0) {
         if (tap < MAXHI && ((hmask >> tap) & 1)) {
           const int j = wave + 8 * tap, cn = min(c + 1, nchunk - 1);
@@ -666,7 +624,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
 #pragma unroll
       for (int tap = 0; tap < TAPS; ++tap) {
         const int wslot = tap % NS;
-        if (G8_ABL & 64) abl_c = c;
         // ---- sub-step 0
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         wb = (bb0 ^ 64u) + (uint32_t)(wslot * (BN * BK * 2));
@@ -675,8 +632,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
-            if (!(G8_ABL & 1)) acc[i][j] = TB_MFMA_16x16x32(bf[0][j], af[0][i], acc[i][j]);
-            else asm volatile("" ::"v"(bf[0][j]), "v"(af[0][i]));
+            acc[i][j] = TB_MFMA_16x16x32(bf[0][j], af[0][i], acc[i][j]);
             const int mi = i * NT + j;
 #pragma unroll
             for (int r = 0; r < NR; ++r)
@@ -689,8 +645,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
         __builtin_amdgcn_sched_barrier(0);
         // ---- sub-step 1
         const int ltap = (tap + NS) % TAPS, lc = c + (tap + NS) / TAPS;   // the stage that refills this tap's slot
-        if ((G8_ABL & 2) || ((G8_ABL & 32) && c > c_begin)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else wait_vmcnt(NWALL);   // in flight: the previous tap's youngest pieces; landed (this wave's share): tap + 1's weights, every halo piece before them
+        wait_vmcnt(NWALL);   // in flight: the previous tap's youngest pieces; landed (this wave's share): tap + 1's weights, every halo piece before them
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         frag_rows(tap + 1 < TAPS ? c : c + 1, tap + 1 < TAPS ? tap + 1 : 0);
@@ -700,8 +655,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
-            if (!(G8_ABL & 1)) acc[i][j] = TB_MFMA_16x16x32(bf[1][j], af[1][i], acc[i][j]);
-            else asm volatile("" ::"v"(bf[1][j]), "v"(af[1][i]));
+            acc[i][j] = TB_MFMA_16x16x32(bf[1][j], af[1][i], acc[i][j]);
             const int mi = i * NT + j;
 #pragma unroll
             for (int k = 0; k < NSLOT; ++k)
@@ -744,15 +698,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
       const uint32_t ab_addr = as_addr + (CONV ? (c & 1) : wslot) * (a_elems * 2) + shift * 128;
       const uint32_t wb_addr = ws_addr + wslot * (BN * BK * 2);
       f16x8 af[2][MT], bf[2][NT];
-      if (G8_ABL & 4) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-          for (int j = 0; j < NT; ++j) asm volatile("" : "=v"(bf[s][j]));
-#pragma unroll
-          for (int i = 0; i < MT; ++i) asm volatile("" : "=v"(af[s][i]));
-        }
-      }
       uint32_t a0[MT];
       const uint32_t b0 = wb_addr + boff0, b1 = wb_addr + boff1;
 #pragma unroll
@@ -766,51 +711,31 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
         }
         if constexpr (KH == 2) {   // this wave's half of the k-step only: sub-step kh
 #pragma unroll
-          for (int j = 0; j < NT; ++j)
-            if (!(G8_ABL & 4)) bf[0][j] = lds_read16_off<2048>(kh ? b1 : b0, j);
+          for (int j = 0; j < NT; ++j) bf[0][j] = lds_read16_off<2048>(kh ? b1 : b0, j);
 #pragma unroll
-          for (int i = 0; i < MT; ++i)
-            if (!(G8_ABL & 4)) af[0][i] = lds_read16(kh ? (a0[i] ^ 64) : a0[i]);
+          for (int i = 0; i < MT; ++i) af[0][i] = lds_read16(kh ? (a0[i] ^ 64) : a0[i]);
         } else {
 #pragma unroll
         for (int q = 0; q < SPH; ++q) {
           const int s = h * SPH + q;
 #pragma unroll
-          for (int j = 0; j < NT; ++j)
-            if (!(G8_ABL & 4)) bf[s][j] = lds_read16_off<2048>(s ? b1 : b0, j);
+          for (int j = 0; j < NT; ++j) bf[s][j] = lds_read16_off<2048>(s ? b1 : b0, j);
 #pragma unroll
-          for (int i = 0; i < MT; ++i)
-            if (!(G8_ABL & 4)) af[s][i] = lds_read16(s ? (a0[i] ^ 64) : a0[i]);
+          for (int i = 0; i < MT; ++i) af[s][i] = lds_read16(s ? (a0[i] ^ 64) : a0[i]);
         }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!DMAC && !DMAC2 && !DMACH) {
+        if constexpr (!DMAC && !DMACH) {
 #pragma unroll
           for (int k = 0; k < NSLOT; ++k)
-            if ((h == 0) == (k < SLOTS0) && !(DMACC && ((G8_DMACC_MASK >> k) & 1))) issue_slot(k, lc, ltap, lslot, c, tap, (tap + NS - 1) / TAPS);
-        }
-        int n_ld = 0;   // DMAC: pieces of this step issued here, in the LOAD phase (G8_DMAC_L slots)
-        if constexpr (DMAC && G8_DMAC_L > 0 && MT * NT >= 10 && WN == 2) {
-#pragma unroll
-          for (int k = 0; k < NSLOT && k < G8_DMAC_L; ++k) {
-            issue_slot(k, lc, ltap, lslot, c, tap, 0);
-            n_ld += (lc < nchunk && (k < WI ? wave + 8 * k < NI_W : wave + 8 * (k - WI) < NI_H)) ? 1 : 0;
-          }
+            if ((h == 0) == (k < SLOTS0)) issue_slot(k, lc, ltap, lslot, c, tap, (tap + NS - 1) / TAPS);
         }
         __builtin_amdgcn_sched_barrier(0);
         // after the step's last issue: everything except THIS step's loads has landed (this wave's part), i.e. the next step's stage
         if (h == HALVES - 1) {
           // (NS >= 4, Linear: the stage two steps ahead may stay in flight as well -- what must have landed is the NEXT step's stage)
-          if constexpr (DMACH) {
-            wait_vmcnt(cnt_hist);
-          } else if constexpr (DMAC) {
-            wait_vmcnt(cnt_hist + n_ld);      // (this step's pieces go out in the COMPUTE phase below; in flight: the previous step's)
-          } else if constexpr (DMACC) {
-            int n0 = 0;                // in flight: this step's pieces issued so far (all but the second compute phase's)
-#pragma unroll
-            for (int k = 0; k < NSLOT; ++k)
-              if (k < SLOTS0 || !((G8_DMACC_MASK >> k) & 1)) n0 += conv_slot_issues(k, lc, c, tap);
-            wait_vmcnt(n0);
+          if constexpr (DMAC || DMACH) {
+            wait_vmcnt(cnt_hist);             // (this step's pieces go out in the COMPUTE phase below; in flight: the previous step's)
           } else {
             wait_vmcnt(!CONV && NS >= 4 ? cnt_step + cnt_hist : cnt_step);
             cnt_hist = cnt_step;
@@ -834,20 +759,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
           for (int i = 0; i < MT; ++i)
 #pragma unroll
             for (int j = 0; j < NT; ++j) {  // transposed: rows of D = output columns (from W), columns of D = output rows (from A)
-              if (!(G8_ABL & 1)) acc[i][j] = TB_MFMA_16x16x32(bf[s][j], af[s][i], acc[i][j]);
-              else asm volatile("" ::"v"(bf[s][j]), "v"(af[s][i]));
-              if constexpr (DMACC) {   // this half's slots ((h == 0) == (k < SLOTS0)), spread over the phase's MT NT SPH MFMAs
-                constexpr int NMFc = SPH * MT * NT;
-                const int mi = (q * MT + i) * NT + j + 1;
-                const int kf = h == 0 ? 0 : SLOTS0, kn = h == 0 ? SLOTS0 : NSLOT - SLOTS0;
-#pragma unroll
-                for (int k = 0; k < NSLOT; ++k)
-                  if (k >= kf && k < kf + kn && ((G8_DMACC_MASK >> k) & 1) && mi == ((k - kf + 1) * NMFc) / (kn + 1)) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    issue_conv_slot_asm(k, lc, ltap, lslot, c, tap);
-                    __builtin_amdgcn_sched_barrier(0);
-                  }
-              }
+              acc[i][j] = TB_MFMA_16x16x32(bf[s][j], af[s][i], acc[i][j]);
               if constexpr (DMACH) {
                 constexpr int NMFh = SPH * MT * NT;
                 const int mi = (q * MT + i) * NT + j + 1;
@@ -859,23 +771,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
                     __builtin_amdgcn_sched_barrier(0);
                   }
               }
-              if constexpr (DMAC2) {   // first compute phase: every piece of the next stage
-                constexpr int NMF2 = SPH * MT * NT;
+              if constexpr (DMAC) {
                 const int mi = (q * MT + i) * NT + j + 1;
 #pragma unroll
                 for (int k = 0; k < NSLOT; ++k)
-                  if (h == 0 && mi == ((k + 1) * NMF2) / (NSLOT + 1)) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    issue_slot_asm(k, lc, lslot);
-                    __builtin_amdgcn_sched_barrier(0);
-                  }
-              }
-              if constexpr (DMAC) {
-                const int mi = (q * MT + i) * NT + j + 1;
-                constexpr int KF = (G8_DMAC_L > 0 && MT * NT >= 10 && WN == 2) ? (G8_DMAC_L < NSLOT ? G8_DMAC_L : NSLOT) : 0;   // slots already issued in the LOAD phase
-#pragma unroll
-                for (int k = KF; k < NSLOT; ++k)
-                  if (mi == ((k - KF + 1) * NMF) / (NSLOT - KF + 1)) {
+                  if (mi == ((k + 1) * NMF) / (NSLOT + 1)) {
                     __builtin_amdgcn_sched_barrier(0);
                     issue_slot_asm(k, lc, lslot);
                     __builtin_amdgcn_sched_barrier(0);
@@ -1028,14 +928,13 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
             for (int e = 0; e < 8; ++e) {
               oh[e] = (f16)(rs[1] * (alpha * (e < 4 ? h0[e] : h1[e - 4]) - rs[0] * ch[e]) + bh[e]);
               og8[e] = (f16)(rs[1] * (alpha * (e < 4 ? g0[e] : g1[e - 4]) - rs[0] * cgv[e]) + bg[e]);
-              oo[e] = (f16)((float)oh[e] * ((G8_ABL & 16) ? (float)og8[e] : gelu_erf_f((float)og8[e])));  // gate on the fp16-rounded projections, as an fp16 module would
+              oo[e] = (f16)((float)oh[e] * gelu_erf_f((float)og8[e]));  // gate on the fp16-rounded projections, as an fp16 module would
             }
-            if ((G8_ABL & 8) && alpha != 12345.f) continue;  // profiling: no global stores
             if (C2g) {
-              G8_ST((f16x8*)(C2g + m * ldc2), oh);
-              G8_ST((f16x8*)(C2g + m * ldc2 + 32), og8);
+              *(f16x8*)(C2g + m * ldc2) = oh;
+              *(f16x8*)(C2g + m * ldc2 + 32) = og8;
             }
-            G8_ST((f16x8*)(Cg + m * ldc), oo);
+            *(f16x8*)(Cg + m * ldc) = oo;
           }
         }
       }
@@ -1088,8 +987,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
               dh[e] = (f16)(v * ge);
               dg[e] = (f16)(v * (float)hv[it][e] * dge);
             }
-            G8_ST((f16x8*)(Cg + m * ldc), dh);
-            G8_ST((f16x8*)(Cg + m * ldc + 32), dg);
+            *(f16x8*)(Cg + m * ldc) = dh;
+            *(f16x8*)(Cg + m * ldc + 32) = dg;
           }
         }
       }
@@ -1373,7 +1272,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const tb_gemm_desc p, int
                 if (RS_OK) ssum += (float)o[e], ssq += (float)o[e] * (float)o[e];
               }
             }
-            if (!(G8_ABL & 8) || alpha == 12345.f) G8_ST((f16x8*)(Cg + m * ldc), o);
+            *(f16x8*)(Cg + m * ldc) = o;
             if (rs_prod) red[row * UPR + cg] = f32x2r_t{ssum, ssq};
           }
         }
@@ -1479,7 +1378,7 @@ int launch8(const tb_gemm_desc& d, hipStream_t s, int wshift, int S = 1) {
   // 162.4 -> 156 us (960 -> 320): 1800 -> 1546 shader cycles per tap against 1304 of MFMAs -- and the clock inside the launch falls from 1.63 to
   // 1.46 GHz: on real operand data these tiles sit at the board's power limit, cycles saved come back as clock.  In the sustained step
   // (scratch/ab_step.py): 27.92 ms with the phases, 27.99 ms with the stream.  Default: the phases.
-  constexpr bool CAN_ST = G8_STREAM && CONV && SUB == 0 && MT >= 4 && NT <= 5 && NS == 3 && KH == 1;
+  constexpr bool CAN_ST = CONV && SUB == 0 && MT >= 4 && NT <= 5 && NS == 3 && KH == 1;
   const bool phases = CAN_ST && !(g8_enable & 1048576);
   static bool attr_done = false;
   if (!attr_done && !g8_dry) {

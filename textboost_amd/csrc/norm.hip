@@ -6,7 +6,6 @@
 // Replaces torch.nn.GroupNorm / F.silu / torch.nn.LayerNorm (and their autograd) that diffusers' ResnetBlock2D,
 // Transformer2DModel, BasicTransformerBlock and transformers' CLIPEncoderLayer dispatch from
 // train_textboost.py:1063-1067 (forward) and :1108 (backward).
-#define TB_GN_INBLOCK 1  // A/B on MI355X (same box, bench.py): in-block finalize +0.6 % steps/s vs a separate finalize launch
 #include "common.h"
 #include "../../include/textboost_hip.h"
 
@@ -32,16 +31,10 @@ struct GnMap {  // thread -> (column-vector, row-lane) mapping shared by the fou
 // leaves >= 640 blocks over the batch (fatter blocks amortise the block reduction and shorten the per-block finalize loop over the
 // chunk partials; A/B on one MI355X, fwd+bwd: 4096x320 77 -> 61 us, 4096x640 113 -> 94 us, 1024x1280 85 -> 61 us; fewer than
 // ~600 blocks under-fills the 256 CUs and loses again)
-#ifndef TB_GN_RU
-#define TB_GN_RU 1   // rows per trip of the two-pass backward kernels' row loops (A/B build switch)
-#endif
 __host__ __device__ inline int gn_chunks(int B, int HW, int C) {
   int cols = C >> 3;
   int cw = cols < 256 ? cols : 256;
   int nrl = 256 / cw;
-#ifdef TB_GN_ROWS
-  int n = (HW + nrl * TB_GN_ROWS - 1) / (nrl * TB_GN_ROWS);
-#else
   int n = (HW + nrl * 4 - 1) / (nrl * 4);
   for (int r = 16; r > 4; r >>= 1) {
     const int nr = (HW + nrl * r - 1) / (nrl * r);
@@ -50,7 +43,6 @@ __host__ __device__ inline int gn_chunks(int B, int HW, int C) {
       break;
     }
   }
-#endif
   int cap = 2048 / (B > 0 ? B : 1);
   if (cap < 1) cap = 1;
   if (n > cap) n = cap;
@@ -123,6 +115,8 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ X
 
 // per-(b, group) totals of the chunk partials, 8 lanes per group + LDS tree (fixed order -> deterministic).
 // mode 0 (forward): out = (mean, rstd);  mode 1 (backward): out = (sum1 / n, sum2 / n)
+// The stand-alone finalize launch of the first version: nothing launches it since gn_block_finalize below replaced it (A/B on MI355X, same box,
+// bench.py: in-block +0.6 % steps/s).  It is still compiled into the code object, which its removal would change.
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ out, int HW, int C, int G,
                                                           int nchunks, float eps, int mode) {
   __shared__ float ls[8][64], lq[8][64];
@@ -165,7 +159,6 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   }
 }
 
-#ifdef TB_GN_INBLOCK
 // In-block version of the finalize step (saves a launch): all 256 threads sum the chunk partials of this image's groups
 __device__ __forceinline__ void gn_block_finalize(const float* __restrict__ part, int b, int HW, int C, int G, int nchunks, float eps,
                                                   int mode, float* o0_s, float* o1_s, float (*ls)[64], float (*lq)[64]) {
@@ -202,7 +195,6 @@ __device__ __forceinline__ void gn_block_finalize(const float* __restrict__ part
     __syncthreads();
   }
 }
-#endif
 
 __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ X, int64_t ldx, f16* __restrict__ Y, int64_t ldy,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -212,20 +204,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ X
   const GnMap mp(C);
   const int chunk = blockIdx.x, b = blockIdx.y;
   const int gs = C / G;
-#ifdef TB_GN_INBLOCK
   __shared__ float ls[8][64], lq[8][64];
   gn_block_finalize(part, b, HW, C, G, nchunks, eps, 0, mean_s, rstd_s, ls, lq);
   if (chunk == 0 && threadIdx.x < G) {
     stats[((int64_t)b * G + threadIdx.x) * 2 + 0] = mean_s[threadIdx.x];
     stats[((int64_t)b * G + threadIdx.x) * 2 + 1] = rstd_s[threadIdx.x];
   }
-#else
-  if (threadIdx.x < G) {
-    mean_s[threadIdx.x] = stats[((int64_t)b * G + threadIdx.x) * 2 + 0];
-    rstd_s[threadIdx.x] = stats[((int64_t)b * G + threadIdx.x) * 2 + 1];
-  }
-  __syncthreads();
-#endif
   if (!mp.active) return;
   const int rpc = (HW + nchunks - 1) / nchunks;
   const int r_begin = chunk * rpc, r_end = min(HW, r_begin + rpc);
@@ -301,20 +285,9 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const f16* __restrict
         }
       };
       int r = r_begin + mp.rl;
-#if TB_GN_RU > 1
-      // TB_GN_RU rows per trip, every load of the trip issued before the first use: a thread of the rolled loop kept one row of x and dy in
-      // flight (32 B), i.e. ~20 KB per CU -- at ~2 us of memory latency that alone bounds the pass near 2.8 TB/s
-      for (; r + (TB_GN_RU - 1) * mp.nrl < r_end; r += TB_GN_RU * mp.nrl) {
-        f16x8 xv[TB_GN_RU], dv[TB_GN_RU];
-#pragma unroll
-        for (int u = 0; u < TB_GN_RU; ++u) {
-          xv[u] = *(const f16x8*)(xb + (int64_t)(r + u * mp.nrl) * ldx + cc * 8);
-          dv[u] = *(const f16x8*)(dyb + (int64_t)(r + u * mp.nrl) * lddy + cc * 8);
-        }
-#pragma unroll
-        for (int u = 0; u < TB_GN_RU; ++u) body(xv[u], dv[u]);
-      }
-#endif
+      // One row per trip.  The rolled loop keeps one row of x and dy in flight per thread (32 B), i.e. ~20 KB per CU -- at ~2 us of memory latency
+      // that alone bounds the pass near 2.8 TB/s; yet 4 / 8 rows per trip with every load of the trip issued before the first use measured
+      // 37.0 / 43.1 us against 37.8 at 8 x 4096 x 320 (neutral / slower), and were removed.
       for (; r < r_end; r += mp.nrl) {
         f16x8 xv = *(const f16x8*)(xb + (int64_t)r * ldx + cc * 8);
         f16x8 dv = *(const f16x8*)(dyb + (int64_t)r * lddy + cc * 8);
@@ -335,16 +308,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const f16* __restrict
   const GnMap mp(C);
   const int chunk = blockIdx.x, b = blockIdx.y;
   const int gs = C / G;
-#ifdef TB_GN_INBLOCK
   __shared__ float ls[8][64], lq[8][64];
   gn_block_finalize(part, b, HW, C, G, nchunks, 0.f, 1, s1_s, s2_s, ls, lq);
-#else
-  if (threadIdx.x < G) {  // part = finalized per-(b, group) means of dyh and dyh*xhat
-    s1_s[threadIdx.x] = part[((int64_t)b * G + threadIdx.x) * 2 + 0];
-    s2_s[threadIdx.x] = part[((int64_t)b * G + threadIdx.x) * 2 + 1];
-  }
-  __syncthreads();
-#endif
   if (!mp.active) return;
   const int rpc = (HW + nchunks - 1) / nchunks;
   const int r_begin = chunk * rpc, r_end = min(HW, r_begin + rpc);
@@ -383,19 +348,6 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const f16* __restrict
       *(f16x8*)(dxb + (int64_t)r * lddx + cc * 8) = o;
     };
     int r = r_begin + mp.rl;
-#if TB_GN_RU > 1
-    for (; r + (TB_GN_RU - 1) * mp.nrl < r_end; r += TB_GN_RU * mp.nrl) {   // (see gn_bwd_stats_kernel)
-      f16x8 xv[TB_GN_RU], dv[TB_GN_RU], av[TB_GN_RU];
-#pragma unroll
-      for (int u = 0; u < TB_GN_RU; ++u) {
-        xv[u] = *(const f16x8*)(xb + (int64_t)(r + u * mp.nrl) * ldx + cc * 8);
-        dv[u] = *(const f16x8*)(dyb + (int64_t)(r + u * mp.nrl) * lddy + cc * 8);
-        if (ab) av[u] = *(const f16x8*)(ab + (int64_t)(r + u * mp.nrl) * ldadd + cc * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < TB_GN_RU; ++u) body(r + u * mp.nrl, xv[u], dv[u], av[u]);
-    }
-#endif
     for (; r < r_end; r += mp.nrl) {
       f16x8 xv = *(const f16x8*)(xb + (int64_t)r * ldx + cc * 8);
       f16x8 dv = *(const f16x8*)(dyb + (int64_t)r * lddy + cc * 8);
@@ -426,14 +378,11 @@ __device__ __forceinline__ void gnf_block_sum2(float& a, float& b, float* red /*
 // Workgroup -> (image, group), XCD-aware (workgroup w runs on XCD w & 7): a group's slice of a pixel row is 80 ... 320 bytes of a 128-byte-line
 // tensor, so neighbouring groups share lines; with the (G, B) grid of the first version neighbours sat on DIFFERENT XCDs and every shared line
 // was fetched into two L2s (1.8x the bytes from HBM for 40-channel groups of fp32 k-slices, 2.6x for the fp16 rows).  Here every XCD owns a
-// contiguous run of slices (a whole image at B = 8), the lines meet in one L2.  TB_GNF_XCD=0 at build time restores the plain order (A/B).
-#ifndef TB_GNF_XCD
-#define TB_GNF_XCD 1
-#endif
+// contiguous run of slices (a whole image at B = 8), the lines meet in one L2.
 __device__ __forceinline__ void gnf_slice_of_block(int G, int& b, int& g) {
   const int n = gridDim.x, bid = blockIdx.x;
   int sl = bid;
-  if (TB_GNF_XCD && (n & 7) == 0) sl = (bid & 7) * (n >> 3) + (bid >> 3);
+  if ((n & 7) == 0) sl = (bid & 7) * (n >> 3) + (bid >> 3);
   b = sl / G;
   g = sl - b * G;
 }
@@ -467,9 +416,6 @@ __device__ __forceinline__ void gnf_splitk_load_all(const GnSplitK& k, int b, in
     const int r = itc / cv, c = itc - r * cv;
     col[i] = g * gs + c * 8;
     off[i] = ((int64_t)b * HW + r) * k.npad + col[i];
-#ifdef TB_GNF_FAKE  // timing experiment only (wrong results): the slices as if laid out [b][g][HW][gs], contiguous per workgroup
-    off[i] = ((int64_t)b * (k.npad / gs) + g) * HW * gs + (int64_t)itc * 8;
-#endif
     roff[i] = ((int64_t)b * HW + r) * k.ldr + col[i];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
@@ -1144,9 +1090,6 @@ extern "C" int tb_groupnorm_fwd(const void* x, int64_t ldx, void* y, int64_t ldy
     return TB_OK;
   }
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nch, B), dim3(256), 0, s, (const f16*)x, ldx, ws, HW, C, G, nch);
-#ifndef TB_GN_INBLOCK
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, ws, stats, HW, C, G, nch, eps, 0);
-#endif
   hipLaunchKernelGGL(gn_apply_kernel, dim3(nch, B), dim3(256), 0, s, (const f16*)x, ldx, (f16*)y, ldy, gamma, beta, ws, stats, HW, C,
                      G, nch, eps, silu);
   TB_CHECK_LAUNCH();
@@ -1179,14 +1122,8 @@ extern "C" int tb_groupnorm_bwd(const void* dy, int64_t lddy, const void* x, int
   }
   hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(nch, B), dim3(256), 0, s, (const f16*)dy, lddy, (const f16*)x, ldx, gamma, beta, stats,
                      ws, HW, C, G, nch, silu);
-#ifdef TB_GN_INBLOCK
-  float* fin = ws;
-#else
-  float* fin = ws + (int64_t)B * nch * G * 2;  // finalized sums live behind the partials
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, ws, fin, HW, C, G, nch, 0.f, 1);
-#endif
   hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(nch, B), dim3(256), 0, s, (const f16*)dy, lddy, (const f16*)x, ldx, gamma, beta, stats,
-                     fin, (const f16*)add, ldadd, (f16*)dx, lddx, HW, C, G, nch, silu);
+                     ws, (const f16*)add, ldadd, (f16*)dx, lddx, HW, C, G, nch, silu);
   TB_CHECK_LAUNCH();
   return TB_OK;
 }
