@@ -1,6 +1,6 @@
-"""A/B of BUILD-time switches inside one process: one TextBoostStep per variant (module attributes set before build_step), both captured as
-graphs, sustained interleaved replays (as scratch/ab_step.py).
-usage: ab_build.py name:mod.ATTR=val[,mod.ATTR=val..] ...      e.g.  base:unet.FOLD_LN=0 fold:unet.FOLD_LN=1"""
+"""Sustained timing of the captured step, one TextBoostStep per variant in one process (interleaved replays, as scratch/ab_step.py); a variant
+sets module attributes before build_step.  scratch/ab_lib.sh runs it once per library (TB_LIB_SUFFIX) with an empty variant.
+usage: ab_build.py name:[mod.ATTR=val[,mod.ATTR=val..]] ...      e.g.  base: nodefer:ops.DEFER_SPLITK=0"""
 import importlib, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

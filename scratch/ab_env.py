@@ -1,5 +1,5 @@
 """A/B of an environment switch read at import / construction time: each variant runs in its own process (fresh import), alternating, on the
-same box.  usage: python scratch/ab_env.py TB_FUSE_LN 0 1 [rounds]"""
+same box.  usage: python scratch/ab_env.py HIP_FORCE_DEV_KERNARG 0 1 [rounds]"""
 import os, subprocess, sys
 var, vals = sys.argv[1], sys.argv[2:4]
 rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 2

@@ -351,9 +351,8 @@ def test_flat_layout_puts_the_magnitudes_behind_the_adapters_and_before_the_adde
         H = te._dora_of(n)
         k = H.mag.numel()
         assert H.mag.data_ptr() == step.flat_lora[o:].data_ptr() and H.grad_mag.data_ptr() == step.flat_grad[o:].data_ptr(), n
-        assert step.grads_p[4][n].data_ptr() == step.flat_grad_p[o:].data_ptr() and step.grads_p[4][n].shape == H.mag.shape, n
         o += k
-    assert te.grad_added.data_ptr() == step.flat_grad[o:].data_ptr() and step.grads_p[2].data_ptr() == step.flat_grad_p[o:].data_ptr()
+    assert te.grad_added.data_ptr() == step.flat_grad[o:].data_ptr()
     assert te.mag.abs().min() > 0                              # the masters moved into the flat buffer with their values
 
 

@@ -592,7 +592,7 @@ def test_split_k_slices_added_by_the_groupnorm_behind_the_convolution(B, Cin, Co
 
 def test_unet_with_and_without_deferred_split_k_reduction_is_bit_equal():
     """the whole executor (SD-shaped tiny UNet at B = 8, where the 8x8 / 4x4 maps split K): forward and dgrad backward with the reducer launches
-    (TB_DEFER_SPLITK=0 behaviour) and with the GroupNorm launches adding the slices must give identical bits"""
+    (ops.DEFER_SPLITK = False) and with the GroupNorm launches adding the slices must give identical bits"""
     import sys, os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from test_gpu_model import make_unet

@@ -64,6 +64,37 @@ def test_kernel_sources_keep_only_the_product_and_profiling_build_switches():
     assert seen == allowed, allowed - seen
 
 
+def test_python_reads_only_the_product_and_diagnostic_environment_variables():
+    # the Python half of the same rule: no A/B switch is read from the environment.  What is left selects a build (TB_LIB_SUFFIX, TB_CFLAGS,
+    # TB_SKIP_BF16), a diagnostic (TB_REC_SHAPES), a documented numeric mode (TB_SEPARATE_TEACHER) or a benchmark variant (bench.py).
+    import ast
+    allowed = {"TB_LIB_SUFFIX", "TB_CFLAGS", "TB_SKIP_BF16", "TB_REC_SHAPES", "TB_SEPARATE_TEACHER", "TB_FORCE_DIST", "TB_GEMM_VARIANT"}
+    files = []
+    for base, dirs, names in os.walk(ROOT):
+        dirs[:] = [d for d in dirs if not d.startswith((".", "_")) and not (base == ROOT and d in ("tests", "scratch"))]
+        files += [os.path.join(base, n) for n in names if n.endswith(".py")]
+    assert len(files) >= 30
+
+    def is_environ(node):
+        return (isinstance(node, ast.Attribute) and node.attr == "environ") or (isinstance(node, ast.Name) and node.id == "environ")
+
+    seen = {}
+    for f in sorted(files):
+        for node in ast.walk(ast.parse(open(f).read(), f)):
+            key = None
+            if isinstance(node, ast.Subscript) and is_environ(node.value):
+                key = node.slice
+            elif isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and is_environ(node.func.value) and node.args:
+                key = node.args[0]      # environ.get / pop / setdefault
+            elif isinstance(node, ast.Call) and getattr(node.func, "attr", getattr(node.func, "id", None)) == "getenv" and node.args:
+                key = node.args[0]
+            elif isinstance(node, ast.Compare) and any(is_environ(c) for c in node.comparators):
+                key = node.left         # "NAME" in os.environ
+            if isinstance(key, ast.Constant) and isinstance(key.value, str) and key.value.startswith("TB_"):
+                seen.setdefault(key.value, os.path.relpath(f, ROOT))
+    assert set(seen) == allowed, ({n: seen[n] for n in set(seen) - allowed}, allowed - set(seen))
+
+
 def test_half_kind_switch_selects_the_library_and_the_dtype():
     from textboost_amd import _lib
     assert _lib.half_kind() == "fp16" and _lib.half_dtype() == torch.float16

@@ -182,7 +182,8 @@ class SplitKPartials:
         self.ws, self.S, self.npad, self.bias, self.rowbias, self.R, self.out = ws, S, npad, bias, rowbias, R, out
 
 
-DEFER_SPLITK = os.environ.get("TB_DEFER_SPLITK", "1") == "1"   # A/B switch: 0 = every split-K launch runs its reducer
+# False = every split-K launch runs its reducer (tests/test_gpu_gemm.py sets it for the bit-equality reference of the deferred sums)
+DEFER_SPLITK = True
 
 
 def gemm(A, W, out, *, K=None, A2=None, W2=None, bias=None, rowbias=None, rows_per_group=0, R=None, act=L.ACT_NONE,

@@ -23,7 +23,6 @@ Trainable state lives in three flat fp32 buffers so the optimizer / all-reduce s
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
@@ -34,7 +33,6 @@ from . import _lib as L
 from . import ops
 
 EOS_ID = 49407  # textboost/text_encoder.py:71
-CHAIN_LORA_BWD = os.environ.get("TB_CHAIN_LORA_BWD", "1") != "0"   # A/B knob: 0 = one dt/dB + one dA launch per layer
 
 
 @dataclass
@@ -373,20 +371,14 @@ class HipTextEncoder:
         if self.n_added:
             self.grad_added.zero_()
 
-    def backward(self, d_out, slot=0, pins=True, grads=None):
+    def backward(self, d_out, slot=0, pins=True):
         """d_out: fp32 [B*T, D] gradient of the (scaled) loss w.r.t. forward(slot)'s output. Accumulates into
-        grad_A / grad_B / grad_added -- or into `grads` = (grad_A, grad_B, grad_added[, {extra module: (grad_A, grad_B)}]) when given: two backward passes that run
-        CONCURRENTLY on two streams (the trainer's instance-prompt and prior-prompt chains) must not add into the same buffers.
-        All scratch is keyed by `slot` for the same reason."""
+        grad_A / grad_B / grad_added (and the extra modules' / DoRA magnitudes' gradient buffers).  All scratch is keyed by `slot`."""
         assert self.mode in ("autocast", "fp32")
-        grad_A, grad_B, grad_added = grads[:3] if grads is not None else (self.grad_A if self.r else None, self.grad_B if self.r else None,
-                                                                          self.grad_added if self.n_added else None)
+        grad_A, grad_B, grad_added = self.grad_A if self.r else None, self.grad_B if self.r else None, self.grad_added if self.n_added else None
         xl = self.extra
-        assert grads is None or not xl or len(grads) >= 4, "an encoder with extra adapted modules needs their gradient buffers too"
-        grad_x = grads[3] if grads is not None and xl else {n: (X.grad_A, X.grad_B) for n, X in xl.items()}
-        # DoRA: grads = (grad_A, grad_B, grad_added, {extra module: (grad_A, grad_B)} or {}, {"qkv" | extra module: grad_mag})
-        assert grads is None or not self.use_dora or len(grads) == 5, "a DoRA encoder needs the magnitude gradient buffers too"
-        grad_m = grads[4] if grads is not None and self.use_dora else {n: self._dora_of(n).grad_mag for n in self.dora_modules()}
+        grad_x = {n: (X.grad_A, X.grad_B) for n, X in xl.items()}
+        grad_m = {n: self._dora_of(n).grad_mag for n in self.dora_modules()}
         full32 = self.mode == "fp32"
         geo, T = self.geo, self.T
         D, I, H = geo.hidden_size, geo.intermediate_size, geo.num_heads
@@ -473,7 +465,7 @@ class HipTextEncoder:
                     else:
                         ops.gemm(dqkv, self.w2_t[i], dt)
                         ops.lora_wide_wgrad(dqkv, x1, self._bufs[p + "t"][:M], dt, grad_A[i], grad_B[i], D, D, self.r, self.rp, 3, self.scaling)
-                elif full32 or not CHAIN_LORA_BWD:
+                elif full32:
                     dt = self.buf(gs + "dt", M, 64, f16)
                     ops.lora_bwd(dqkv, x1, self._bufs[p + "t"][:M], self.lora_B[i], dt, grad_A[i], grad_B[i], D, D, self.r, 3,
                                  self.scaling, w2_fwd=self.w2_fwd[i])

@@ -27,35 +27,6 @@ from . import _lib as L
 from . import ops
 
 
-import os as _os
-# GEGLU backward fused into the ff.net.2 dgrad GEMM's epilogue: with the lean wide-tile epilogue it saves the d(gated) round trip
-# (A/B in one process: 35.23 -> 35.06 ms per step); through the 4-wave kernels' generic epilogue it was slower than the streaming kernel
-FUSE_GEGLU_BWD = _os.environ.get("TB_FUSE_GEGLU_BWD", "1") == "1"
-# the whole GEGLU feed-forward of the C = 320 blocks as one launch per direction (csrc/ff_fused.hip): the gated tensor / d(proj) never go to memory
-FUSE_FF = _os.environ.get("TB_FUSE_FF", "1") == "1"
-FUSE_FF_LN = _os.environ.get("TB_FUSE_FF_LN", "1") == "1"   # the fused feed-forward backward also applies norm3's LayerNorm backward (A/B switch)
-# round 6: the fused feed-forward's launch also runs its row-local neighbours (ops.ff_fwd pre / post): bit 1 = attn2.to_out + residual + norm3 in
-# front, bit 2 = proj_out + residual behind (A/B switch)
-FF_CHAIN = int(_os.environ.get("TB_FF_CHAIN", "3"))
-# ... and the two Linear -> LayerNorm -> Linear pairs of a 64x64-map block as one launch each (ops.chain320): bit 1 = proj_in -> norm1 -> qkv,
-# bit 2 = attn1.to_out + residual -> norm2 -> attn2.to_q
-ROW_CHAIN = int(_os.environ.get("TB_ROW_CHAIN", "3"))
-MATERIALIZE_UPSAMPLE = _os.environ.get("TB_MATERIALIZE_UPSAMPLE", "1") == "1"  # A/B switch (see the up-block forward)
-# LayerNorm fused into the neighbouring Linear's epilogue where a tile spans the row (C = 320, the 64x64 maps): forward into the producer of the
-# residual stream, backward onto the accumulators of the dgrad GEMM that feeds it (round 3; 28 LayerNorm launches per step fewer)
-FUSE_LN = _os.environ.get("TB_FUSE_LN", "1") == "1"
-# round 5: where no tile spans the row (C = 640 / 1280), the block's three LayerNorms are FOLDED into the Linear behind each of them (gamma into the
-# frozen weight, mean / rstd as per-row scalars of the consumer's epilogue, row statistics written by the producer of the residual stream):
-# no LayerNorm launch and no normalised copy in the forward (A/B switch)
-FOLD_LN = _os.environ.get("TB_FOLD_LN", "1") == "1"
-# Upsampler convolutions (nearest x2 + conv3x3) as four 2x2-tap sub-pixel convolutions with pre-summed frozen weights (round 4): 2.25x fewer FLOP in
-# the forward and in the dgrad, no materialised 4x map, no 2x2 gradient pooling pass.  The summed filter rows are rounded to fp16 once: a stated
-# divergence from the 9-tap arithmetic, bounded in tests/test_gpu_gemm.py.  TB_SUBPIXEL=0 restores the materialised-upsample path (A/B).
-SUBPIXEL = _os.environ.get("TB_SUBPIXEL", "1") == "1"
-# the downsamplers' input gradient as a sub-pixel convolution of d out (ops.pack_strided_dgrad_subpixel); 0 = the 4-wave transposed gather
-DOWN_DGRAD_SUBPIXEL = _os.environ.get("TB_DOWN_DGRAD_SUBPIXEL", "1") == "1"
-
-
 @dataclass
 class UNetGeometry:
     in_channels: int = 4
@@ -298,7 +269,10 @@ class HipUNet:
                 lin(prefix + ".conv_shortcut")
             self.resnets.append(prefix)
 
-        self.fold_slots: Dict[str, int] = {}   # transformer prefix -> statistic slots per row (> 0: its LayerNorms are folded, see FOLD_LN)
+        # Where no tile spans the row (C = 640 / 1280), a block's three LayerNorms were FOLDED into the Linear behind each of them in round 5 (gamma
+        # into the frozen weight, mean / rstd as per-row scalars of the consumer's epilogue, row statistics written by the producer of the residual
+        # stream): no LayerNorm launch and no normalised copy in the forward.
+        self.fold_slots: Dict[str, int] = {}   # transformer prefix -> statistic slots per row (> 0: its LayerNorms are folded)
 
         def transformer(prefix, C, level):
             norm(prefix + ".norm")
@@ -316,7 +290,7 @@ class HipUNet:
             lin(f"{tb}.ff.net.2")
             M = self.B * (self.H >> level) * (self.W >> level)
             slots = 0
-            if FOLD_LN and wdt != torch.float32 and not (FUSE_LN and ops.gemm_ln_ok(M, C, C, wdt)):
+            if wdt != torch.float32 and not ops.gemm_ln_ok(M, C, C, wdt):
                 slots = ops.lnfold_slots(M, C, wdt)
             self.fold_slots[prefix] = slots
             if slots:
@@ -347,8 +321,9 @@ class HipUNet:
             if i < len(ch) - 1:
                 conv(f"down_blocks.{i}.downsamplers.0.conv")
                 name = f"down_blocks.{i}.downsamplers.0.conv"
-                # the stride-2 convolution's input gradient as a sub-pixel convolution over d out (csrc/gemm8.hip SUB = 1) where the coarse map tiles
-                if DOWN_DGRAD_SUBPIXEL and wdt != torch.float32 and ops.subpixel_ok(self.B, self.H >> (i + 1), self.W >> (i + 1), c, c, wdt):
+                # the stride-2 convolution's input gradient as a sub-pixel convolution over d out (csrc/gemm8.hip SUB = 1) where the coarse map tiles;
+                # elsewhere (and in fp32 mode) the backward falls back to the 4-wave transposed gather
+                if wdt != torch.float32 and ops.subpixel_ok(self.B, self.H >> (i + 1), self.W >> (i + 1), c, c, wdt):
                     P[name + ".wdsub2"] = ops.pack_strided_dgrad_subpixel(sd[name + ".weight"].to(dev).to(wdt))
                 skip_chs.append(c)
             prev = c
@@ -369,6 +344,10 @@ class HipUNet:
             if i < len(ch) - 1:
                 conv(f"up_blocks.{i}.upsamplers.0.conv")
                 name = f"up_blocks.{i}.upsamplers.0.conv"
+                # Upsampler convolutions (nearest x2 + conv3x3) as four 2x2-tap sub-pixel convolutions with pre-summed frozen weights (round 4): 2.25x
+                # fewer FLOP in the forward and in the dgrad, no materialised 4x map, no 2x2 gradient pooling pass.  The summed filter rows are rounded
+                # to fp16 once: a stated divergence from the 9-tap arithmetic, bounded in tests/test_gpu_gemm.py.  Where the map does not tile (and in
+                # fp32 mode) no packed weight exists and the 9-tap paths of forward / backward run.
                 if wdt != torch.float32 and ops.subpixel_ok(self.B, self.H >> level, self.W >> level, c, c, wdt):
                     P[name + ".wsub"], P[name + ".wdsub"] = ops.pack_subpixel_weights(sd[name + ".weight"].to(dev).to(wdt))
             prev = c
@@ -476,9 +455,13 @@ class HipUNet:
         n0 = self.scratch("a", M, C)
         self._gn_fwd(x, prefix + ".norm", n0, st0, HW, False, eps=1e-6, partials=x_partials)  # (x_partials: see _resnet)
         t0 = self.buf(prefix + ".t0", M, C)
-        fuse_ln = FUSE_LN and ops.gemm_ln_ok(M, C, C, self.dtype)
-        # folded LayerNorms (FOLD_LN, decided in _pack): the producers of the residual stream (proj_in, attn1.to_out, attn2.to_out) write per-tile row
-        # statistics (rs), the Linear behind each LayerNorm multiplies the RAW stream by gamma-folded weights and normalises in its epilogue
+        # Three LayerNorm dispatches, by shape and numeric mode:
+        #   fuse_ln -- a tile spans the row (C = 320, the 64x64 maps): LayerNorm in the neighbouring Linear's epilogue, forward into the producer of the
+        #              residual stream, backward onto the accumulators of the dgrad GEMM that feeds it (round 3: 28 LayerNorm launches per step fewer);
+        #   fold    -- C = 640 / 1280 (decided in _pack): the producers of the residual stream (proj_in, attn1.to_out, attn2.to_out) write per-tile row
+        #              statistics (rs), the Linear behind each LayerNorm multiplies the RAW stream by gamma-folded weights and normalises in its epilogue;
+        #   neither -- fp32 mode and off-grid shapes: plain LayerNorm launches.
+        fuse_ln = ops.gemm_ln_ok(M, C, C, self.dtype)
         fold = self.fold_slots.get(prefix, 0)
         assert not (fold and fuse_ln)
         rs = self.scratch("rs", M, 16 * 2, torch.float32).view(M, 16, 2) if fold else None
@@ -486,25 +469,24 @@ class HipUNet:
         # --- self attention
         ls1 = self.buf(prefix + ".ls1", M, 2, torch.float32)
         qkv = self.buf(prefix + ".qkv", M, 3 * C)
+        # round 6: proj_in -> norm1 -> qkv as ONE launch on the 64x64 maps (csrc/chain320.hip): a 128-row tile spans the 320-wide rows of all three
+        # layers, LayerNorm(t0) never goes to memory.  Together with chain_b below it took the step from 28.41 to 28.35 ms.
+        chain_a = fuse_ln and ops.chain320_ok(M, 3 * C, self.dtype)
         if fold:
             ops.gemm(n0, P[prefix + ".proj_in.w"], t0, bias=P[prefix + ".proj_in.b"], rs_out=rs, rs_slots=fold)
             ops.gemm(t0, P[tb + ".attn1.qkv.w"], qkv, bias=P[tb + ".attn1.qkv.c2"], lnfold=(rs, fold, P[tb + ".attn1.qkv.c1"], ls1, 1e-5))
+        elif chain_a:
+            ops.chain320(n0, P[prefix + ".proj_in.w"], P[prefix + ".proj_in.b"], None, t0, P[tb + ".norm1.g"], P[tb + ".norm1.b"], ls1,
+                         P[tb + ".attn1.qkv.w"], None, qkv)
         else:
-            # round 6 (ROW_CHAIN): proj_in -> norm1 -> qkv as ONE launch on the 64x64 maps (csrc/chain320.hip): a 128-row tile spans the 320-wide rows of
-            # all three layers, LayerNorm(t0) never goes to memory
-            chain_a = ROW_CHAIN & 1 and fuse_ln and ops.chain320_ok(M, 3 * C, self.dtype)
-            if chain_a:
-                ops.chain320(n0, P[prefix + ".proj_in.w"], P[prefix + ".proj_in.b"], None, t0, P[tb + ".norm1.g"], P[tb + ".norm1.b"], ls1,
-                             P[tb + ".attn1.qkv.w"], None, qkv)
+            l1 = self.scratch("a2" if fuse_ln else "a", M, C)   # (fused: written while n0 -- scratch "a" -- is still being read)
+            if fuse_ln:
+                ops.gemm(n0, P[prefix + ".proj_in.w"], t0, bias=P[prefix + ".proj_in.b"],
+                         ln_fwd=(P[tb + ".norm1.g"], P[tb + ".norm1.b"], ls1, l1, 1e-5))
             else:
-                l1 = self.scratch("a2" if fuse_ln else "a", M, C)   # (fused: written while n0 -- scratch "a" -- is still being read)
-                if fuse_ln:
-                    ops.gemm(n0, P[prefix + ".proj_in.w"], t0, bias=P[prefix + ".proj_in.b"],
-                             ln_fwd=(P[tb + ".norm1.g"], P[tb + ".norm1.b"], ls1, l1, 1e-5))
-                else:
-                    ops.gemm(n0, P[prefix + ".proj_in.w"], t0, bias=P[prefix + ".proj_in.b"])
-                    ops.layernorm_fwd(t0, l1, P[tb + ".norm1.g"], P[tb + ".norm1.b"], ls1)
-                ops.gemm(l1, P[tb + ".attn1.qkv.w"], qkv)
+                ops.gemm(n0, P[prefix + ".proj_in.w"], t0, bias=P[prefix + ".proj_in.b"])
+                ops.layernorm_fwd(t0, l1, P[tb + ".norm1.g"], P[tb + ".norm1.b"], ls1)
+            ops.gemm(l1, P[tb + ".attn1.qkv.w"], qkv)
         o1 = self.buf(prefix + ".o1", M, C)
         lse1 = self.buf(prefix + ".lse1", B * heads, HW, torch.float32)
         fp8_ws = None
@@ -517,23 +499,22 @@ class HipUNet:
         # --- cross attention (K/V hoisted)
         ls2 = self.buf(prefix + ".ls2", M, 2, torch.float32)
         q2 = self.buf(prefix + ".q2", M, C)
+        chain_b = fuse_ln and ops.chain320_ok(M, C, self.dtype)   # attn1.to_out + residual -> norm2 -> attn2.to_q, one launch
         if fold:
             ops.gemm(o1, P[tb + ".attn1.to_out.0.w"], t1, bias=P[tb + ".attn1.to_out.0.b"], R=t0, rs_out=rs, rs_slots=fold)
             ops.gemm(t1, P[tb + ".attn2.to_q.w"], q2, bias=P[tb + ".attn2.to_q.c2"], lnfold=(rs, fold, P[tb + ".attn2.to_q.c1"], ls2, 1e-5))
+        elif chain_b:
+            ops.chain320(o1, P[tb + ".attn1.to_out.0.w"], P[tb + ".attn1.to_out.0.b"], t0, t1, P[tb + ".norm2.g"], P[tb + ".norm2.b"], ls2,
+                         P[tb + ".attn2.to_q.w"], None, q2)
         else:
-            chain_b = ROW_CHAIN & 2 and fuse_ln and ops.chain320_ok(M, C, self.dtype)   # attn1.to_out + residual -> norm2 -> attn2.to_q, one launch
-            if chain_b:
-                ops.chain320(o1, P[tb + ".attn1.to_out.0.w"], P[tb + ".attn1.to_out.0.b"], t0, t1, P[tb + ".norm2.g"], P[tb + ".norm2.b"], ls2,
-                             P[tb + ".attn2.to_q.w"], None, q2)
+            l2 = self.scratch("a", M, C)
+            if fuse_ln:
+                ops.gemm(o1, P[tb + ".attn1.to_out.0.w"], t1, bias=P[tb + ".attn1.to_out.0.b"], R=t0,
+                         ln_fwd=(P[tb + ".norm2.g"], P[tb + ".norm2.b"], ls2, l2, 1e-5))
             else:
-                l2 = self.scratch("a", M, C)
-                if fuse_ln:
-                    ops.gemm(o1, P[tb + ".attn1.to_out.0.w"], t1, bias=P[tb + ".attn1.to_out.0.b"], R=t0,
-                             ln_fwd=(P[tb + ".norm2.g"], P[tb + ".norm2.b"], ls2, l2, 1e-5))
-                else:
-                    ops.gemm(o1, P[tb + ".attn1.to_out.0.w"], t1, bias=P[tb + ".attn1.to_out.0.b"], R=t0)
-                    ops.layernorm_fwd(t1, l2, P[tb + ".norm2.g"], P[tb + ".norm2.b"], ls2)
-                ops.gemm(l2, P[tb + ".attn2.to_q.w"], q2)
+                ops.gemm(o1, P[tb + ".attn1.to_out.0.w"], t1, bias=P[tb + ".attn1.to_out.0.b"], R=t0)
+                ops.layernorm_fwd(t1, l2, P[tb + ".norm2.g"], P[tb + ".norm2.b"], ls2)
+            ops.gemm(l2, P[tb + ".attn2.to_q.w"], q2)
         self._ensure_kv()
         ko = self.kv_off[tb + ".attn2"]
         k2, v2 = self.kv_all[:, ko:ko + C], self.kv_all[:, ko + C:ko + 2 * C]
@@ -548,16 +529,14 @@ class HipUNet:
         t2 = self.buf(prefix + ".t2", M, C)
         # --- GEGLU feed-forward
         ls3 = self.buf(prefix + ".ls3", M, 2, torch.float32)
-        l3 = None
-        fuse_ff = FUSE_FF and not fold and ops.ff_fused_ok(M, C, 4 * C, self.dtype)
-        # round 6 (FF_CHAIN bits: 1 = attn2.to_out + residual + norm3 in FRONT of the fused feed-forward, 2 = proj_out + residual BEHIND it, in the same
-        # launch): a 128-row tile spans the 320-wide rows of all four layers, so l3 and t3 never leave the CU
-        chain = FF_CHAIN if (fuse_ff and fuse_ln and self.dtype != torch.float32) else 0
+        # the whole GEGLU feed-forward of the C = 320 blocks as one launch per direction (csrc/ff_fused.hip): the gated tensor / d(proj) never go to memory
+        fuse_ff = not fold and ops.ff_fused_ok(M, C, 4 * C, self.dtype)
+        # round 6: attn2.to_out + residual + norm3 in FRONT of the fused feed-forward and proj_out + residual BEHIND it ride in the same launch: a
+        # 128-row tile spans the 320-wide rows of all four layers, so l3 and t3 never leave the CU (28.17 -> 28.08 ms per step)
+        chain = fuse_ff and fuse_ln and self.dtype != torch.float32
         if fold:
             ops.gemm(o2, P[tb + ".attn2.to_out.0.w"], t2, bias=P[tb + ".attn2.to_out.0.b"], R=t1, rs_out=rs, rs_slots=fold)
-        elif chain & 1:
-            pass   # (issued with the feed-forward below)
-        else:
+        elif not chain:   # (chained: issued with the feed-forward below)
             l3 = self.scratch("a", M, C)
             if fuse_ln:
                 ops.gemm(o2, P[tb + ".attn2.to_out.0.w"], t2, bias=P[tb + ".attn2.to_out.0.b"], R=t1,
@@ -567,11 +546,9 @@ class HipUNet:
                 ops.layernorm_fwd(t2, l3, P[tb + ".norm3.g"], P[tb + ".norm3.b"], ls3)
         raw = self.buf(prefix + ".raw", M, 8 * C)
         if chain:
-            pre = (P[tb + ".attn2.to_out.0.w"], P[tb + ".attn2.to_out.0.b"], t1, t2, P[tb + ".norm3.g"], P[tb + ".norm3.b"], ls3, 1e-5) if chain & 1 else None
-            post = (P[prefix + ".proj_out.w"], P[prefix + ".proj_out.b"], x, out) if chain & 2 else None
-            t3 = None if chain & 2 else self.scratch("a2", M, C)
-            ops.ff_fwd(o2 if chain & 1 else l3, P[tb + ".ff1.w"], P[tb + ".ff1.b"], P[tb + ".ff.net.2.w"], P[tb + ".ff.net.2.b"], raw, t3, R=t2,
-                       pre=pre, post=post)
+            pre = (P[tb + ".attn2.to_out.0.w"], P[tb + ".attn2.to_out.0.b"], t1, t2, P[tb + ".norm3.g"], P[tb + ".norm3.b"], ls3, 1e-5)
+            post = (P[prefix + ".proj_out.w"], P[prefix + ".proj_out.b"], x, out)
+            ops.ff_fwd(o2, P[tb + ".ff1.w"], P[tb + ".ff1.b"], P[tb + ".ff.net.2.w"], P[tb + ".ff.net.2.b"], raw, None, R=t2, pre=pre, post=post)
         elif fold:
             gated = self.scratch("b", M, 4 * C)
             ops.gemm(t2, P[tb + ".ff1.w"], gated, bias=P[tb + ".ff1.c2"], act=L.ACT_GEGLU, C2=raw, lnfold=(rs, fold, P[tb + ".ff1.c1"], ls3, 1e-5))
@@ -585,7 +562,7 @@ class HipUNet:
             ops.gemm(l3, P[tb + ".ff1.w"], gated, bias=P[tb + ".ff1.b"], act=L.ACT_GEGLU, C2=raw)
             t3 = self.scratch("a", M, C)
             ops.gemm(gated, P[tb + ".ff.net.2.w"], t3, bias=P[tb + ".ff.net.2.b"], R=t2)
-        if not (chain & 2):
+        if not chain:
             ops.gemm(t3, P[prefix + ".proj_out.w"], out, bias=P[prefix + ".proj_out.b"], R=x)
         stop_after_cross = (tb + ".attn2") == self.first_xattn
 
@@ -593,20 +570,13 @@ class HipUNet:
             dt3 = self.scratch("g1", M, C)
             ops.gemm(dout, P[prefix + ".proj_out.wd"], dt3)
             dt2 = self.scratch("g3", M, C)
-            if fuse_ff and FUSE_FF_LN:   # ... and the LayerNorm backward of norm3 in its epilogue (round 5): dt2 = LN'(dl3) + dt3 directly
+            if fuse_ff:   # ff.net.2 dgrad, GEGLU backward, ff.net.0 dgrad and (round 5) norm3's LayerNorm backward in one launch: dt2 = LN'(dl3) + dt3
                 ops.ff_bwd(dt3, P[tb + ".ff.net.2.wd"], P[tb + ".ff1.wd"], raw, dt2, R=dt3, ln=(t2, ls3, ln_g("norm3")))
-            elif fuse_ff:   # ff.net.2 dgrad, GEGLU backward and ff.net.0 dgrad in one launch; the LayerNorm backward behind it
-                dl3 = self.scratch("g2", M, C)
-                ops.ff_bwd(dt3, P[tb + ".ff.net.2.wd"], P[tb + ".ff1.wd"], raw, dl3)
-                ops.layernorm_bwd(dl3, t2, ln_g("norm3"), ls3, dt2, add=dt3)
             else:
                 dproj = self.scratch("gc", M, 8 * C)
-                if FUSE_GEGLU_BWD or self.dtype == torch.float32:   # ff.net.2 dgrad with the GEGLU backward fused into its epilogue
-                    ops.gemm(dt3, P[tb + ".ff.net.2.wd"], dproj, act=L.ACT_GEGLU_GRAD, C2=raw)
-                else:
-                    dgated = self.scratch("gb", M, 4 * C)
-                    ops.gemm(dt3, P[tb + ".ff.net.2.wd"], dgated)
-                    ops.geglu_bwd(dgated, raw, dproj)
+                # ff.net.2 dgrad with the GEGLU backward in its epilogue: with the lean wide-tile epilogue it saved the d(gated) round trip of the
+                # streaming kernel (A/B in one process: 35.23 -> 35.06 ms per step; through the 4-wave kernels' generic epilogue it had been slower)
+                ops.gemm(dt3, P[tb + ".ff.net.2.wd"], dproj, act=L.ACT_GEGLU_GRAD, C2=raw)
                 if fuse_ln:
                     ops.gemm(dproj, P[tb + ".ff1.wd"], dt2, R=dt3, ln_bwd=(P[tb + ".norm3.g"], ls3, t2))
                 else:
@@ -794,18 +764,18 @@ class HipUNet:
                 nb, nhc = cats[(i + 1, 0)]
                 dst = nb[:, :nhc]
                 name = f"up_blocks.{i}.upsamplers.0.conv"
-                if SUBPIXEL and (name + ".wsub") in P:
+                if (name + ".wsub") in P:
                     # four 2x2-tap convolutions on the COARSE map, each writing one parity class of the fine map (csrc/gemm8.hip, SUB = 1)
                     ops.gemm(x, P[name + ".wsub"], dst, bias=P[name + ".b"],
                              conv=dict(B=B, Hin=hw[lvl][0], Win=hw[lvl][1], Cin=x.shape[1], Hout=hw[lvl - 1][0], Wout=hw[lvl - 1][1], stride=1,
                                        sign=1, upsample=2, transposed=0))
-                elif MATERIALIZE_UPSAMPLE and hw[lvl - 1][1] % 16 == 0:
+                elif hw[lvl - 1][1] % 16 == 0:
                     # nearest x2 written out (12 us for the largest map), so that the halo-resident wide-tile kernel takes the convolution
                     # instead of the 4-wave gather with the upsampling folded in (311 -> ~205 us at 64x64 x 640 channels)
                     xu = self.scratch("up2x", Ms[lvl - 1], x.shape[1])
                     ops.upsample2x(x, xu, B, hw[lvl][0], hw[lvl][1], x.shape[1])
                     self._conv(xu, name, dst, B, hw[lvl - 1][0], hw[lvl - 1][1], hw[lvl - 1][0], hw[lvl - 1][1], bias=P[name + ".b"])
-                else:
+                else:   # a fine map whose width is no multiple of 16: the 4-wave gather with the upsampling folded in
                     self._conv(x, name, dst, B, hw[lvl][0], hw[lvl][1], hw[lvl - 1][0], hw[lvl - 1][1], upsample=1, bias=P[name + ".b"])
                 up_records.append(("up", (name, lvl), x, dst, None))
                 x = dst
@@ -844,7 +814,7 @@ class HipUNet:
             if kind == "up":
                 name, lvl = fn
                 gx = self.buf(f"grad.up.{name}", M, cin)
-                if SUBPIXEL and (name + ".wdsub") in self.P:
+                if (name + ".wdsub") in self.P:
                     # dgrad of the sub-pixel convolutions: the fine gradient read as four strided views, 16 taps per coarse pixel (SUB = 2)
                     ops.gemm(g, self.P[name + ".wdsub"], gx,
                              conv=dict(B=B, Hin=hw[lvl - 1][0], Win=hw[lvl - 1][1], Cin=g.shape[1], Hout=hw[lvl][0], Wout=hw[lvl][1], stride=1,
