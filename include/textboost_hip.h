@@ -331,6 +331,15 @@ int tb_attn_token_maps(const tb_attn_desc* d, int dtype, int b0, int nb, float w
  * (one small copy behind the stream's queued work) unless the stream is being captured, where nothing may synchronise: the kernel then
  * treats a value >= 32 as a region no query belongs to.  No atomics, every output has one owner: a repeated launch is bit-identical. */
 int tb_attention_region_fwd(const tb_attn_desc* d, int dtype, const int32_t* key_region, const uint32_t* query_regions, tb_stream_t stream);
+/* Two-term short-key attention forward (csrc/p2p_attn.hip; prompt-to-prompt editing):
+ *   O(d1) = softmax(d1.scale Q1 K1^T) V1 + softmax(d2.scale Q2 K2^T) V2
+ * each softmax normalised over its own keys, the sum taken in fp32 and rounded once (P is normalised before it is rounded to 16 bits).
+ * d2 == NULL gives the single term.  Reads Q / K / V, their leading dimensions (any >= H * hd, any row alignment), Skv, scale and causal of
+ * both descriptors, B, H, Sq, hd of both (they must agree) and O / ldo of d1; d2's O and the LSE fields are not read, no LSE is written.
+ * dtype is the operands' (TB_F16 only); hd % 8 == 0, hd <= 160, 1 <= Skv <= 128 for each term (they may differ), any Sq, causal == 0;
+ * anything else -- mismatched descriptors included -- returns -22 and launches nothing.  No atomics, every output has one owner: a repeated
+ * launch is bit-identical.  Nothing is read back to the host (safe inside a stream capture). */
+int tb_attention_dual_fwd(const tb_attn_desc* d1, const tb_attn_desc* d2, int dtype, tb_stream_t stream);
 
 /* ---- scheduler / boundary / loss / misc streaming kernels ------------------------------------------ */
 /* noise_scheduler.add_noise (:1052) [+ get_velocity (:1073) when velocity != NULL]; fp32 NCHW in, fp16 noisy out */

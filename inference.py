@@ -6,6 +6,7 @@ textboost_amd/generate.py.
         [--checkpoint N] [--with <output_dir> ...] [--weights W ...]
         [--init-image photo.jpg [--strength S] [--mask mask.png | --mask auto:WORD [--dilate PX]] [--no-paste]]
         [--region "WORDS=x0,y0,x1,y1" | --region "WORDS=@mask.png" ...] [--region-steps F]
+        [--edit-prompt TEXT] [--reweight WORD=F ...] [--cross-steps F] [--self-steps F]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -45,6 +46,17 @@ size instead of a box (resized to the latent grid, white = inside).  --region-st
 ceil(F * executed steps) steps only (default: all).  `<output stem>_regions.png` shows the regions as flat colours at the image's size.
 Works with --with and with --init-image / --mask; not with --attn-map (the recorder recomputes an unmasked softmax and would report
 attention that did not happen).
+
+--edit-prompt TEXT changes the prompt and keeps the picture (textboost_amd/p2p.py; Prompt-to-Prompt, Hertz et al. 2022):
+`--prompt "a photo of a dog on a beach" --edit-prompt "a photo of a <dog> dog on a beach"` generates both prompts side by side from each
+seed's latent; for the first --cross-steps F of the steps (default 0.8) the edited image's cross-attention reuses the source image's
+probabilities for the words the prompts share (a swapped word takes the place of the word it replaces, an added word attends on its own),
+and for the first --self-steps F (default 0.4) its self-attention on the coarse maps (a quarter of the latent side and smaller) reuses the
+source's maps.  --reweight WORD=F (repeatable, 0 <= F <= 10) multiplies the attention to a word of the edit prompt; with only --reweight
+the edit prompt is the prompt.  The output is a 2 x seeds grid, the source row on top and the edited row below (without --output the edited
+images are written as `<edit prompt>_<seed>_edit.jpg`).  Both prompts go through one text-encoder call.  Works with --with; not with
+--init-image (a photo would have to be inverted first), --region or --attn-map (the recorder recomputes its own softmax and would report
+attention that did not happen).  The default fractions are the paper's; they have not been measured on pretrained weights here.
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
@@ -95,6 +107,14 @@ def build_parser():
                    help="confine these words of the prompt to a box x0,y0,x1,y1 (fractions of the image) or to @mask.png; repeatable")
     p.add_argument("--region-steps", dest="region_steps", type=float, default=None, metavar="F",
                    help="with --region: the regions act on the first ceil(F * executed steps) steps, 0 < F <= 1 (default 1)")
+    p.add_argument("--edit-prompt", dest="edit_prompt", type=str, default=None, metavar="TEXT",
+                   help="also generate this prompt from the same noise, keeping the layout of --prompt's image (prompt-to-prompt)")
+    p.add_argument("--cross-steps", dest="cross_steps", type=float, default=None, metavar="F",
+                   help="with --edit-prompt / --reweight: cross-attention control on the first floor(F * steps) steps, 0 <= F <= 1 (default 0.8)")
+    p.add_argument("--self-steps", dest="self_steps", type=float, default=None, metavar="F",
+                   help="with --edit-prompt / --reweight: self-attention control on the first floor(F * steps) steps, 0 <= F <= 1 (default 0.4)")
+    p.add_argument("--reweight", dest="reweight", type=str, action="append", default=None, metavar="WORD=F",
+                   help="multiply the attention to this word of the edit prompt by F, 0 <= F <= 10; repeatable")
     return p
 
 
@@ -132,7 +152,9 @@ def load_runs(args):
             first.setdefault(n, r.path)
     for tok, dropped in run.shadowed:
         for what, text in [("--prompt", args.prompt)] + [("--attn-map", w) for w in (args.attn_map or [])] + \
-                [("--region", r) for r in (getattr(args, "region", None) or [])]:
+                [("--region", r) for r in (getattr(args, "region", None) or [])] + \
+                [("--edit-prompt", t) for t in [getattr(args, "edit_prompt", None)] if t is not None] + \
+                [("--reweight", r) for r in (getattr(args, "reweight", None) or [])]:
             if tok in text:
                 raise SystemExit(f"inference.py: {what} {text!r} uses {tok}, which both {first[tok]} and {dropped} hold: ambiguous (the first "
                                  "run's vector would be taken); rename the token in one run or leave it out of the prompt")
@@ -223,6 +245,52 @@ def check_region_args(args, run, edit):
     return {"regions": regions, "steps": steps}
 
 
+def check_p2p_flags(args):
+    """--edit-prompt / --reweight / --cross-steps / --self-steps: the refusals that need no file, by flag name.  -> is this an edit?"""
+    from textboost_amd import p2p as P
+    editing = args.edit_prompt is not None or bool(args.reweight)
+    if not editing:
+        for flag, given in (("--cross-steps", args.cross_steps is not None), ("--self-steps", args.self_steps is not None)):
+            if given:
+                raise SystemExit(f"inference.py: {flag} needs --edit-prompt TEXT or --reweight WORD=F (the edit it controls)")
+        return False
+    flag = "--edit-prompt" if args.edit_prompt is not None else "--reweight"
+    if args.init_image is not None:
+        raise SystemExit(f"inference.py: {flag} does not go with --init-image: editing a photo by its prompt would need the photo inverted to "
+                         "noise first, which is not built; use --init-image with --mask, or generate the source from a seed")
+    if args.region:
+        raise SystemExit(f"inference.py: {flag} does not go with --region: both take over the cross-attention launch")
+    if args.attn_map is not None:
+        raise SystemExit(f"inference.py: {flag} does not go with --attn-map: the recorder recomputes its own softmax from q and k, so it would "
+                         "report attention that did not happen under the control")
+    try:
+        for name, f in (("--cross-steps", args.cross_steps), ("--self-steps", args.self_steps)):
+            if f is not None:
+                P.steps_for(f, args.steps, name)
+        for r in args.reweight or []:
+            P.parse_reweight(r)
+    except P.P2PError as e:
+        raise SystemExit(f"inference.py: {e}")
+    return True
+
+
+def check_p2p_args(args, run):
+    """the token plan, on the host, before any model is built.  -> None or {"plan": p2p.P2PPlan, "edit_prompt": str, "cross": F, "self": F}"""
+    from textboost_amd import p2p as P
+    if not check_p2p_flags(args):
+        return None
+    edit_prompt = args.prompt if args.edit_prompt is None else args.edit_prompt
+    try:
+        from textboost_amd.attn_maps import run_tokenizer
+        pl = P.plan(run_tokenizer(args.model, run), args.prompt, edit_prompt, model_text_len(args.model), [P.parse_reweight(r) for r in args.reweight or []])
+    except P.P2PError as e:
+        raise SystemExit(f"inference.py: {e}")
+    except OSError as e:
+        raise SystemExit(f"inference.py: --edit-prompt: {e} (--model must be a local diffusers model directory)")
+    return {"plan": pl, "edit_prompt": edit_prompt, "cross": P.CROSS_STEPS if args.cross_steps is None else args.cross_steps,
+            "self": P.SELF_STEPS if args.self_steps is None else args.self_steps}
+
+
 def regions_path(args):
     stem = os.path.splitext(args.output)[0] if args.output is not None else args.prompt.replace(" ", "_")
     return stem + "_regions.png"
@@ -293,17 +361,20 @@ def main(argv=None):
     if not args.model:
         raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
     G.check_model_dir(args.model, "inference.py")
+    check_p2p_flags(args)
     run = load_runs(args)
     words = positions = None
     if args.attn_map is not None:        # every refusal before anything reaches the device
         words, positions = attn_map_words(args.model, run, args.prompt, args.attn_map)
     edit = check_edit_args(args)
     region = check_region_args(args, run, edit)
+    p2p = check_p2p_args(args, run)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("inference.py needs an MI355X: the product path has no CPU fallback")
     from textboost_amd import augment
-    n = len(args.seeds)
+    nseeds = len(args.seeds)
+    n = 2 * nseeds if p2p is not None else nseeds      # prompt-to-prompt: the source rows, then the edited rows
     with torch.no_grad():
         pipe = G.Pipeline.from_model_dir(args.model, n, steps=args.steps, guidance=7.5)
         base = G.load_base_text(args.model)
@@ -325,9 +396,10 @@ def main(argv=None):
             print(f"wrote {auto_mask_path(args)}: {A.describe(auto_mask, stats)}")
             del maker
         T = base.geo.max_pos
-        ids = G.tokenize(tokenizer, [""] * n + [args.prompt] * n, T).to(pipe.dev)
+        prompts = [args.prompt] * n if p2p is None else [args.prompt] * nseeds + [p2p["edit_prompt"]] * nseeds
+        ids = G.tokenize(tokenizer, [""] * n + prompts, T).to(pipe.dev)
         states = te.forward(ids, pins=False).view(2, n * T, -1)
-        latents = torch.cat([G.seeded_latent(s, pipe.size) for s in args.seeds]).to(pipe.dev)
+        latents = torch.cat([G.seeded_latent(s, pipe.size) for s in args.seeds] * (n // nseeds)).to(pipe.dev)
         recorder = None
         if words is not None:
             from textboost_amd.attn_maps import AttnMapRecorder
@@ -337,8 +409,13 @@ def main(argv=None):
             from textboost_amd import regions as R
             rset, rsteps = R.RegionSet.for_unet(pipe.unet, region["regions"]), region["steps"]
         what = f"prompt {args.prompt!r}, seeds {args.seeds}"
+        ctl = None
+        if p2p is not None:
+            from textboost_amd.p2p import P2PControl
+            ctl = P2PControl.for_unet(pipe.unet, p2p["plan"], cross_steps=p2p["cross"], self_steps=p2p["self"])
+            what += f", edit prompt {p2p['edit_prompt']!r}"
         if edit is None:
-            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps)
+            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps, p2p=ctl)
         else:       # a seed's latent is the noise of its image; the photo is encoded once
             import numpy as np
             from textboost_amd import edit as E
@@ -370,16 +447,18 @@ def main(argv=None):
         print(f"wrote {regions_path(args)}: " + "; ".join(f"{' '.join(r.words)} -> {int(r.cells.sum())} of {r.cells.size} latent cells, "
                                                            f"token positions {list(r.positions)}" for r in region["regions"]))
     if args.output is not None:
-        grid = Image.new("RGB", (n * images[0].width, images[0].height))     # diffusers.utils.make_image_grid(images, 1, n)
+        rows = n // nseeds                                                    # 2 with --edit-prompt: the source row, then the edited row
+        grid = Image.new("RGB", (nseeds * images[0].width, rows * images[0].height))     # diffusers.utils.make_image_grid(images, rows, nseeds)
         for k, im in enumerate(images):
-            grid.paste(im, box=(k * im.width, 0))
+            grid.paste(im, box=((k % nseeds) * im.width, (k // nseeds) * im.height))
         grid.save(args.output)
         print(f"wrote {args.output}")
         if word_maps is not None:
             write_attn_maps(os.path.splitext(args.output)[0] + "_attn", images, word_maps, words, args.seeds)
     else:
-        for seed, im in zip(args.seeds, images):
-            out = args.prompt.replace(" ", "_") + f"_{seed}.jpg"
+        for k, im in enumerate(images):
+            seed = args.seeds[k % nseeds]
+            out = args.prompt.replace(" ", "_") + f"_{seed}.jpg" if k < nseeds else p2p["edit_prompt"].replace(" ", "_") + f"_{seed}_edit.jpg"
             im.save(out)
             print(f"wrote {out}")
         if word_maps is not None:

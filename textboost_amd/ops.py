@@ -505,6 +505,21 @@ def attention_region_fwd(q, k, v, o, lse, B, H, Sq, Skv, hd, key_region, query_r
     return o
 
 
+def attention_dual_fwd(q1, k1, v1, q2, k2, v2, o, B, H, Sq, Skv1, Skv2, hd, scale=None):
+    """o = softmax(scale q1 k1^T) v1 + softmax(scale q2 k2^T) v2 in attention_fwd's layout, for short key sequences (Skv1, Skv2 <= 128;
+    csrc/p2p_attn.hip): each softmax normalised over its own keys, the sum taken in fp32 and rounded once.  q2 = None: the single term
+    (k2 / v2 / Skv2 are then ignored).  No LSE is written."""
+    two = q2 is not None
+    ts = (q1, k1, v1, o) + ((q2, k2, v2) if two else ())
+    assert all(t.stride(1) == 1 and t.dtype == q1.dtype for t in ts)
+    sc = scale if scale is not None else hd ** -0.5
+    d1 = _attn_desc(q1, k1, v1, o, None, B, H, Sq, Skv1, hd, sc, False)
+    d2 = _attn_desc(q2, k2, v2, o, None, B, H, Sq, Skv2, hd, sc, False) if two else None   # (its O is not read)
+    with _rec("attn_dual_fwd_kernel", 4.0 * B * H * Sq * (Skv1 + (Skv2 if two else 0)) * hd):
+        _launch("tb_attention_dual_fwd", d1, d2, _dt(q1))
+    return o
+
+
 # ------------------------------------------------------------------ small streaming kernels
 def add_noise(x0, noise, timesteps, acp, noisy, velocity=None):
     B = x0.shape[0]

@@ -180,14 +180,21 @@ class HipSampler:
         self.t_dev = [torch.full((2 * B,), t, dtype=torch.int64, device=dev) for t in self.timesteps]
         self.generator: Optional[torch.Generator] = None
 
-    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None):
+    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None, p2p=None):
         """cond / uncond: fp16 or fp32 [B*77, D] text-encoder outputs.  Returns the final latents fp32 [B,4,h,w].
         step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`.
         maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step.
         regions: a `regions.RegionSet` of this UNet; the first `region_steps` executed steps (default: all) run the region-masked
-        cross-attention, the others the plain one."""
+        cross-attention, the others the plain one.
+        p2p: a `p2p.P2PControl` of this UNet (DPM-Solver++ only).  Rows [0, B/2) are then the source images and [B/2, B) the edited ones (the
+        caller gives both halves the same latents); steps i < floor(cross_steps * steps) run the controlled cross-attention and steps
+        i < floor(self_steps * steps) the controlled self-attention of the edited conditional rows, every other row stays plain.  Not with
+        `maps` (the recorder recomputes an uncontrolled softmax) or `regions` (both take over the edited rows' cross-attention): ValueError."""
         B, sch = self.B, self.sch
+        p2p_cross, p2p_self = self._p2p_steps(p2p, maps, regions)
         region_steps = self._region_steps(regions, region_steps, self.steps)
+        if p2p is not None:
+            p2p.reset()
         if maps is not None:
             maps.zero()
         if latents is None:
@@ -199,7 +206,7 @@ class HipSampler:
         ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
         n = self.x[0].numel()
         for i in range(self.steps):
-            eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None)
+            eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None, p2p, i < p2p_cross, i < p2p_self)
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i)
             if getattr(sch, "needs_noise", False):  # the variance noise of the ancestral step rides in the m_prev operand
@@ -269,18 +276,45 @@ class HipSampler:
             raise ValueError(f"region_steps {region_steps}: a whole number of the {executed} executed steps, 1 .. {executed}")
         return int(region_steps)
 
-    def _unet_forward(self, i, ehs, maps, regions=None):
-        if maps is None and regions is None:
+    def _p2p_steps(self, p2p, maps=None, regions=None):
+        """(steps with cross control, steps with self control) of `denoise`; every refusal, before anything is touched"""
+        if p2p is None:
+            return 0, 0
+        from .p2p import steps_for
+        if maps is not None:
+            raise ValueError("prompt-to-prompt does not go with maps: the recorder recomputes its own softmax from q and k, so it would report "
+                             "attention that did not happen under the control")
+        if regions is not None:
+            raise ValueError("prompt-to-prompt does not go with regions: the control's launch would overwrite the region-masked attention of "
+                             "the edited rows")
+        if not isinstance(self.sch, DPMSolverPP2M):
+            raise NotImplementedError(f"prompt-to-prompt runs on the DPM-Solver++ scheduler only, not on {type(self.sch).__name__}")
+        if self.B % 2:
+            raise ValueError(f"prompt-to-prompt takes an even batch (source rows, then edited rows), not {self.B}")
+        if p2p.B4 != self.unet.B or p2p.T != self.unet.T or (p2p.h, p2p.w) != (self.unet.H, self.unet.W):
+            raise ValueError(f"the prompt-to-prompt control is built for batch {p2p.B4}, {p2p.T} tokens and a {p2p.h} x {p2p.w} grid; the UNet "
+                             f"runs batch {self.unet.B}, {self.unet.T} tokens, {self.unet.H} x {self.unet.W}")
+        return steps_for(p2p.cross_steps, self.steps, "cross_steps"), steps_for(p2p.self_steps, self.steps, "self_steps")
+
+    def _unet_forward(self, i, ehs, maps, regions=None, p2p=None, p2p_cross=False, p2p_self=False):
+        if p2p is not None and not (p2p_cross or p2p_self):
+            p2p = None
+        if maps is None and regions is None and p2p is None:
             return self.unet.forward(self.x2, self.t_dev[i], ehs)
-        prev = self.unet.attn_maps, self.unet.regions
+        prev = self.unet.attn_maps, self.unet.regions, self.unet.p2p
         if maps is not None:
             self.unet.attn_maps = maps
         if regions is not None:
             self.unet.regions = regions
+        if p2p is not None:
+            self.unet.p2p = p2p
+            p2p.cross_active, p2p.self_active = bool(p2p_cross), bool(p2p_self)
         try:
             return self.unet.forward(self.x2, self.t_dev[i], ehs)
         finally:
-            self.unet.attn_maps, self.unet.regions = prev
+            self.unet.attn_maps, self.unet.regions, self.unet.p2p = prev
+            if p2p is not None:
+                p2p.cross_active = p2p.self_active = False
 
     def sample(self, cond_ehs, uncond_ehs, latents=None):
         return self.vae.decode(self.denoise(cond_ehs, uncond_ehs, latents))

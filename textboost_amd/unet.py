@@ -25,6 +25,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .p2p import SELF_MIN_LEVEL
 
 
 @dataclass
@@ -112,6 +113,7 @@ class HipUNet:
         self._fp8_ws = None
         self.attn_maps = None   # an attn_maps.AttnMapRecorder: every cross-attention forward then also records its token maps (opt-in; None = no launch)
         self.regions = None     # a regions.RegionSet: every cross-attention forward then runs the region-masked kernel with that level's table (opt-in; None = the plain forward)
+        self.p2p = None         # a p2p.P2PControl: extra launches overwrite the edited conditional rows of the attention outputs (opt-in; None = the plain forward, launch for launch)
         self.attn_loss = None   # enable_attn_loss(): the cross-attention localisation loss in the backward of the supervised layers (None = no launch)
         self._bufs: Dict[str, torch.Tensor] = {}
         self.tape: List = []
@@ -495,6 +497,11 @@ class HipUNet:
                 self._fp8_ws = ops.attention_fp8_workspace(B, heads, HW, self.dev)  # one scratch, reused by every such layer (stream order)
             fp8_ws = self._fp8_ws
         ops.attention_fwd(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], o1, lse1, B, heads, HW, HW, hd, fp8_ws=fp8_ws)
+        p2p = self.p2p
+        if p2p is not None and p2p.self_active and level >= SELF_MIN_LEVEL:   # prompt-to-prompt (p2p.py): the edited rows attend with the source rows' maps
+            n = p2p.n
+            src, edt = slice(2 * n * HW, 3 * n * HW), slice(3 * n * HW, 4 * n * HW)
+            ops.attention_fwd(qkv[src, :C], qkv[src, C:2 * C], qkv[edt, 2 * C:], o1[edt], lse1[3 * n * heads:], n, heads, HW, HW, hd)
         t1 = self.buf(prefix + ".t1", M, C)
         # --- cross attention (K/V hoisted)
         ls2 = self.buf(prefix + ".ls2", M, 2, torch.float32)
@@ -524,6 +531,12 @@ class HipUNet:
             ops.attention_fwd(q2, k2, v2, o2, lse2, B, heads, HW, T, hd)
         else:   # regional prompting (regions.py): restricted prompt tokens are visible inside their region only
             ops.attention_region_fwd(q2, k2, v2, o2, lse2, B, heads, HW, T, hd, self.regions.key_region, self.regions.table(lvl_hw))
+        if p2p is not None and p2p.cross_active:   # o2[c_edit] = P^s V1 + P^e V2 behind the unchanged all-rows launch (p2p.py)
+            n = p2p.n
+            src, edt = slice(2 * n * HW, 3 * n * HW), slice(3 * n * HW, 4 * n * HW)
+            ksrc, kedt = slice(2 * n * T, 3 * n * T), slice(3 * n * T, 4 * n * T)
+            pv1, pv2 = p2p.values(tb + ".attn2", v2)
+            ops.attention_dual_fwd(q2[src], k2[ksrc], pv1, None if pv2 is None else q2[edt], k2[kedt], pv2, o2[edt], n, heads, HW, T, T, hd)
         if self.attn_maps is not None:
             self.attn_maps.record(q2, k2, heads, lvl_hw, hd)
         t2 = self.buf(prefix + ".t2", M, C)
