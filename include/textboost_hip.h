@@ -385,6 +385,22 @@ int tb_dpm_step_blend(float* x, const void* eps2, float* m_prev, void* x2, int64
 /* dst[y][x] = mask[y][x] ? gen[y][x] : orig[y][x] on resident RGBX images of w x h pixels (strides in pixels), mask u8 (stride in bytes) */
 int tb_img_paste(const uint32_t* gen, int64_t gstride, const uint32_t* orig, int64_t ostride, const uint8_t* mask, int64_t mstride,
                  uint32_t* dst, int64_t dstride, int w, int h, tb_stream_t stream);
+/* ---- editing a photo by its prompt (csrc/invert.hip; inference.py --invert-image, HipSampler.invert / denoise(pin=...)) ----
+ * one step of DDIM inversion with guidance, up the noise schedule: x fp32 [B, n_per_b], eps2 = UNet output in the library's 16-bit type
+ * [2B, n_per_b] (uncond | cond) as in tb_dpm_step;  eps = e_u + g (e_c - e_u);  xn = cx x + ce eps;  x = xn;  x2 = 16-bit (xn | xn), the
+ * rounding of the fp32 value stored in x;  traj_out[b] = xn (fp32 [B, n_per_b]; may be NULL).  (cx, ce) = DPMSolverPP2M.inversion_scalars.
+ * NULL x / eps2 / x2, n_per_b <= 0, B <= 0 or B > 65535: TB_EINVAL, nothing launched. */
+int tb_invert_step(float* x, const void* eps2, void* x2, float* traj_out, int64_t n_per_b, int B, float guidance, float cx, float ce,
+                   tb_stream_t stream);
+/* tb_dpm_step (same arithmetic, same bits in x, m_prev and x2 of an unpinned element), then the select against the photo's trajectory:
+ *   rows b <  n_src:  x[b, j] = pin[j]
+ *   rows b >= n_src:  x[b, j] = (mask == NULL || mask[j % hw]) ? x[b, j] : pin[j]
+ * pin fp32 [n_per_b] (the trajectory at the NEXT level, shared by the rows), mask u8 [hw] or NULL (non-zero = repaint; shared by channels and
+ * rows).  m_prev = the row's own unpinned data prediction everywhere; x2 = 16-bit (x | x): tb_dpm_step's conversion where the step is
+ * kept, half(pin) where the pin is.  NULL x / eps2 / m_prev / x2 / pin, n_per_b <= 0, B <= 0 or B > 65535, alpha_t == 0, n_src outside
+ * 0 .. B, hw <= 0 or n_per_b % hw != 0 (hw is checked with a NULL mask too): TB_EINVAL, nothing launched. */
+int tb_dpm_step_pin(float* x, const void* eps2, float* m_prev, void* x2, int64_t n_per_b, int B, float guidance, float alpha_t, float sigma_t,
+                    float ca, float cb, float cc, const float* pin, int n_src, const uint8_t* mask, int hw, tb_stream_t stream);
 /* (decoded / 2 + 0.5).clamp(0, 1): NHWC fp32 [B*HW, ld >= C] -> NCHW fp32 [B, C, HW] */
 int tb_vae_image(const float* decoded, int64_t ld, float* image, int B, int HW, int C, tb_stream_t stream);
 /* the same decoder output as bytes: decoded fp32 [B*HW, ld >= 3] (R, G, B in the first three columns) -> image u32 [B*HW] in the resident RGBX

@@ -7,6 +7,7 @@ textboost_amd/generate.py.
         [--init-image photo.jpg [--strength S] [--mask mask.png | --mask auto:WORD [--dilate PX]] [--no-paste]]
         [--region "WORDS=x0,y0,x1,y1" | --region "WORDS=@mask.png" ...] [--region-steps F]
         [--edit-prompt TEXT] [--reweight WORD=F ...] [--cross-steps F] [--self-steps F]
+        [--invert-image photo.jpg [--invert-guidance G] [--mask mask.png [--no-paste]]]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -55,8 +56,18 @@ and for the first --self-steps F (default 0.4) its self-attention on the coarse 
 source's maps.  --reweight WORD=F (repeatable, 0 <= F <= 10) multiplies the attention to a word of the edit prompt; with only --reweight
 the edit prompt is the prompt.  The output is a 2 x seeds grid, the source row on top and the edited row below (without --output the edited
 images are written as `<edit prompt>_<seed>_edit.jpg`).  Both prompts go through one text-encoder call.  Works with --with; not with
---init-image (a photo would have to be inverted first), --region or --attn-map (the recorder recomputes its own softmax and would report
+--init-image (a photo has to be inverted first: --invert-image, below), --region or --attn-map (the recorder recomputes its own softmax and would report
 attention that did not happen).  The default fractions are the paper's; they have not been measured on pretrained weights here.
+
+--invert-image FILE edits a real photo by its prompt: `--invert-image photo.jpg --prompt "a photo of a dog on a beach"
+--edit-prompt "a photo of a <dog> dog on a beach"` puts the trained dog into THIS photo.  --prompt describes the photo.  The photo is prepared
+and encoded as for --init-image (the mode, so the run is deterministic), walked up the noise schedule under --prompt (DDIM inversion, --steps
+UNet calls at guidance --invert-guidance G, default 1), and the prompt-to-prompt edit then runs from the noise it arrives at, the source row
+being held on the photo's own trajectory: it ends as the photo's latents exactly.  The output is a 2 x 1 grid, the VAE round trip of the
+prepared photo on top and the edit below (without --output: `<prompt>_inv.jpg` and `<edit prompt>_inv_edit.jpg`); --seeds is not read.
+--mask FILE (the photo's size, white = repaint) keeps the latent cells outside it on the photo's trajectory in the edited row as well, and the
+photo's bytes are pasted outside the mask (--no-paste writes the plain decode).  --reweight, --cross-steps, --self-steps, --with work as with
+--edit-prompt.  Not with --init-image, --strength, --region, --attn-map, --mask auto:WORD or --dilate, and not on a v-prediction model.
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
@@ -115,6 +126,10 @@ def build_parser():
                    help="with --edit-prompt / --reweight: self-attention control on the first floor(F * steps) steps, 0 <= F <= 1 (default 0.4)")
     p.add_argument("--reweight", dest="reweight", type=str, action="append", default=None, metavar="WORD=F",
                    help="multiply the attention to this word of the edit prompt by F, 0 <= F <= 10; repeatable")
+    p.add_argument("--invert-image", dest="invert_image", type=str, default=None, metavar="FILE",
+                   help="with --edit-prompt / --reweight: edit this photo; --prompt describes it, the photo is inverted to noise first")
+    p.add_argument("--invert-guidance", dest="invert_guidance", type=float, default=None, metavar="G",
+                   help="with --invert-image: guidance scale of the inversion, finite and >= 0 (default 1)")
     return p
 
 
@@ -168,7 +183,7 @@ def check_edit_args(args):
     from textboost_amd import edit as E
     if args.init_image is None:
         for flag, given in (("--mask", args.mask is not None), ("--strength", args.strength is not None), ("--dilate", args.dilate is not None)):
-            if given:
+            if given and not (flag == "--mask" and getattr(args, "invert_image", None) is not None):      # (--invert-image takes a mask file too)
                 raise SystemExit(f"inference.py: {flag} needs --init-image FILE (the photo to edit)")
         return None
     strength = DEFAULT_STRENGTH if args.strength is None else args.strength
@@ -274,6 +289,69 @@ def check_p2p_flags(args):
     return True
 
 
+def check_invert_flags(args):
+    """--invert-image / --invert-guidance: the refusals that need no file, by flag name.  -> is this an inversion?"""
+    import math
+    if args.invert_image is None:
+        if args.invert_guidance is not None:
+            raise SystemExit("inference.py: --invert-guidance needs --invert-image FILE (the photo whose inversion it guides)")
+        return False
+    if args.edit_prompt is None and not args.reweight:
+        raise SystemExit("inference.py: --invert-image needs --edit-prompt TEXT or --reweight WORD=F: the photo is inverted to be edited by its "
+                         "prompt (--prompt describes the photo); to restyle a photo without a second prompt use --init-image")
+    why = {"--init-image": "a photo is either inverted or noised to a strength, not both",
+           "--strength": "the inversion walks the whole schedule; a strength belongs to --init-image",
+           "--region": "the edit's control and the regions both take over the cross-attention launch",
+           "--attn-map": "the recorder recomputes its own softmax from q and k, so it would report attention that did not happen under the control",
+           "--dilate": "it grows the mask of --mask auto:WORD, which is not built for an inverted photo"}
+    for flag, given in (("--init-image", args.init_image is not None), ("--strength", args.strength is not None), ("--region", bool(args.region)),
+                        ("--attn-map", args.attn_map is not None), ("--dilate", args.dilate is not None)):
+        if given:
+            raise SystemExit(f"inference.py: --invert-image does not go with {flag}: {why[flag]}")
+    if args.mask is not None and args.mask.startswith("auto:"):
+        raise SystemExit(f"inference.py: --invert-image does not go with --mask {args.mask}: the mask maker noises the photo to one level and is "
+                         "not built for an inverted one; paint a mask and pass --mask FILE")
+    g = args.invert_guidance
+    if g is not None and not (math.isfinite(g) and g >= 0.0):
+        raise SystemExit(f"inference.py: --invert-guidance {g}: a finite number >= 0 (1 inverts under the prompt alone)")
+    return True
+
+
+def check_invert_args(args):
+    """--invert-image: the refusals that read files, on the host, before any model is built.  -> None or {"rgb": uint8 [H, W, 3], "mask": PIL "L"
+    image or None, "guidance": float}"""
+    import json
+    from textboost_amd import edit as E
+    if not check_invert_flags(args):
+        return None
+    cfg = os.path.join(args.model, "scheduler", "scheduler_config.json")
+    if os.path.exists(cfg):
+        with open(cfg) as f:
+            pred = json.load(f).get("prediction_type", "epsilon")
+        if pred != "epsilon":
+            raise SystemExit(f"inference.py: --invert-image: {cfg} says prediction_type {pred!r}; inversion is built for epsilon models only (a v "
+                             "output would have to be converted with the scalars of the level its input is on, which an inversion step is one "
+                             "level off); SD1.x and SD2.1-base are epsilon models")
+    try:
+        rgb = E.load_rgb(args.invert_image)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"inference.py: --invert-image {args.invert_image}: cannot be read as a picture ({e})")
+    mask = None
+    if args.mask is not None:
+        try:
+            mask = E.load_mask(args.mask)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"inference.py: --mask {args.mask}: cannot be read as a picture ({e})")
+        if mask.size != (rgb.shape[1], rgb.shape[0]):
+            raise SystemExit(f"inference.py: --mask {args.mask} is {mask.size[0]} x {mask.size[1]}, --invert-image {args.invert_image} is "
+                             f"{rgb.shape[1]} x {rgb.shape[0]}: the mask must have the photo's size")
+    try:
+        E.check_vae_has_encoder(args.model)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"inference.py: --invert-image: {e}")
+    return {"rgb": rgb, "mask": mask, "guidance": 1.0 if args.invert_guidance is None else args.invert_guidance}
+
+
 def check_p2p_args(args, run):
     """the token plan, on the host, before any model is built.  -> None or {"plan": p2p.P2PPlan, "edit_prompt": str, "cross": F, "self": F}"""
     from textboost_amd import p2p as P
@@ -361,6 +439,7 @@ def main(argv=None):
     if not args.model:
         raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
     G.check_model_dir(args.model, "inference.py")
+    check_invert_flags(args)
     check_p2p_flags(args)
     run = load_runs(args)
     words = positions = None
@@ -369,11 +448,16 @@ def main(argv=None):
     edit = check_edit_args(args)
     region = check_region_args(args, run, edit)
     p2p = check_p2p_args(args, run)
+    invert = check_invert_args(args)
+    seeds = args.seeds
+    if invert is not None:
+        seeds = ["inv"]        # one photo, one deterministic edit: the file names carry `inv` in the seed's place
+        print("--invert-image: --seeds is not read (the photo's inversion is the noise; the encoder's mode makes the run deterministic)")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("inference.py needs an MI355X: the product path has no CPU fallback")
     from textboost_amd import augment
-    nseeds = len(args.seeds)
+    nseeds = len(seeds)
     n = 2 * nseeds if p2p is not None else nseeds      # prompt-to-prompt: the source rows, then the edited rows
     with torch.no_grad():
         pipe = G.Pipeline.from_model_dir(args.model, n, steps=args.steps, guidance=7.5)
@@ -399,7 +483,7 @@ def main(argv=None):
         prompts = [args.prompt] * n if p2p is None else [args.prompt] * nseeds + [p2p["edit_prompt"]] * nseeds
         ids = G.tokenize(tokenizer, [""] * n + prompts, T).to(pipe.dev)
         states = te.forward(ids, pins=False).view(2, n * T, -1)
-        latents = torch.cat([G.seeded_latent(s, pipe.size) for s in args.seeds] * (n // nseeds)).to(pipe.dev)
+        latents = None if invert is not None else torch.cat([G.seeded_latent(s, pipe.size) for s in seeds] * (n // nseeds)).to(pipe.dev)
         recorder = None
         if words is not None:
             from textboost_amd.attn_maps import AttnMapRecorder
@@ -408,13 +492,28 @@ def main(argv=None):
         if region is not None:
             from textboost_amd import regions as R
             rset, rsteps = R.RegionSet.for_unet(pipe.unet, region["regions"]), region["steps"]
-        what = f"prompt {args.prompt!r}, seeds {args.seeds}"
+        what = f"prompt {args.prompt!r}, " + (f"seeds {seeds}" if invert is None else f"photo {args.invert_image}")
         ctl = None
         if p2p is not None:
             from textboost_amd.p2p import P2PControl
             ctl = P2PControl.for_unet(pipe.unet, p2p["plan"], cross_steps=p2p["cross"], self_steps=p2p["self"])
             what += f", edit prompt {p2p['edit_prompt']!r}"
-        if edit is None:
+        if invert is not None:      # the photo is encoded once and inverted under --prompt; the source row is pinned to that trajectory
+            import numpy as np
+            from textboost_amd import edit as E
+            enc = E.EditEncoder(args.model, pipe.size)
+            init_rgbx, pixels = E.prepare_image(invert["rgb"], enc.S)
+            z0 = enc.encode(pixels)
+            del enc
+            latent_mask = pixel_mask = None
+            if invert["mask"] is not None:
+                pm, lm = E.prepare_mask(invert["mask"], init_rgbx.shape[0], cell=init_rgbx.shape[0] // pipe.size)
+                latent_mask = torch.from_numpy(np.ascontiguousarray(lm)).to(pipe.dev)
+                if not args.no_paste:
+                    pixel_mask = torch.from_numpy(np.ascontiguousarray(pm)).to(pipe.dev)
+            rgbx = pipe.invert_edit_images(states[1], states[0], z0, ctl, invert_guidance=invert["guidance"], latent_mask=latent_mask,
+                                           pixel_mask=pixel_mask, init_rgbx=init_rgbx if pixel_mask is not None else None, what=what)
+        elif edit is None:
             rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps, p2p=ctl)
         else:       # a seed's latent is the noise of its image; the photo is encoded once
             import numpy as np
@@ -454,15 +553,15 @@ def main(argv=None):
         grid.save(args.output)
         print(f"wrote {args.output}")
         if word_maps is not None:
-            write_attn_maps(os.path.splitext(args.output)[0] + "_attn", images, word_maps, words, args.seeds)
+            write_attn_maps(os.path.splitext(args.output)[0] + "_attn", images, word_maps, words, seeds)
     else:
         for k, im in enumerate(images):
-            seed = args.seeds[k % nseeds]
+            seed = seeds[k % nseeds]
             out = args.prompt.replace(" ", "_") + f"_{seed}.jpg" if k < nseeds else p2p["edit_prompt"].replace(" ", "_") + f"_{seed}_edit.jpg"
             im.save(out)
             print(f"wrote {out}")
         if word_maps is not None:
-            for k, seed in enumerate(args.seeds):
+            for k, seed in enumerate(seeds):
                 write_attn_maps(args.prompt.replace(" ", "_") + f"_{seed}_attn", images[k:k + 1], word_maps[k:k + 1], words, [seed])
 
 

@@ -7,6 +7,7 @@ eval_dreambooth.py (`load_pipeline` :175-215, `generate_from_pipeline` :218-267,
     Pipeline.from_model_dir(model_dir, ...)     -> UNet, VAE decoder and sampler executors, built once per run
     Pipeline.set_unet_adapters([...])           -> attn2.to_k / to_v = W + sum w_i B_i A_i (one exact-fp32 GEMM, rounded once); [] = the base weights
     Pipeline.edit_images(cond, uncond, noise, z0, strength, ...)  -> `images` from an encoded photo, optionally inside a mask (edit.py)
+    Pipeline.invert_edit_images(cond, uncond, z0, p2p, ...)       -> a photo inverted to noise and edited by its prompt
     generate_instance(pipe, base, run, ...)     -> <outdir>/seed<s>/<instance>/<prompt>.png for every seed, 25 prompts each
 
 Device work: `HipTextEncoder.forward`, `HipSampler.denoise` (guided DPM-Solver++ steps on `HipUNet.forward`), `HipVAEDecoder.decode_rgbx`
@@ -434,6 +435,32 @@ class Pipeline:
             return rgbx
         out = torch.empty_like(rgbx)
         for b in range(rgbx.shape[0]):      # one launch per image
+            ops.img_paste(rgbx[b], init_rgbx, pixel_mask, out=out[b])
+        return out
+
+    def invert_edit_images(self, cond, uncond, z0, p2p, invert_guidance: float = 1.0, latent_mask=None, pixel_mask=None, init_rgbx=None,
+                           what: str = "") -> torch.Tensor:
+        """A photo edited by its prompt: rows [0, B/2) carry the prompt that describes the photo, rows [B/2, B) the edit
+        prompt.  z0 fp32 [1, 4, size, size] (the encoded photo) is inverted under row 0's prompt (`HipSampler.invert`, guidance
+        `invert_guidance`), then the prompt-to-prompt denoise runs with the source rows pinned to that trajectory (`denoise(p2p=, pin=)`):
+        they end as z0 exactly, so their image is the VAE round trip of the photo.  latent_mask uint8 [size, size] or None (non-zero =
+        repaint): the edited rows' other cells stay on the trajectory too.  With pixel_mask (uint8 [8 size, 8 size]) and init_rgbx (the
+        prepared photo, int32 RGBX) the photo's bytes are pasted outside the mask into the EDITED rows only; the source rows stay the plain
+        decode.  -> int32 RGBX [B, 8 size, 8 size] (resident)."""
+        from . import ops
+        if (pixel_mask is None) != (init_rgbx is None):
+            raise ValueError("the paste needs both pixel_mask and init_rgbx")
+        if p2p is None:
+            raise ValueError("invert_edit_images needs the prompt-to-prompt control of the edit")
+        traj = self.sampler.invert(cond, uncond, z0, guidance=invert_guidance)
+        x = self.sampler.denoise(cond, uncond, p2p=p2p, pin=traj[:, 0], pin_mask=latent_mask)
+        if not bool(torch.isfinite(x).all()):
+            raise FloatingPointError(f"non-finite latents after {self.steps} inversion and {self.steps} denoising steps: {what}")
+        rgbx = self.vae.decode_rgbx(x)
+        if pixel_mask is None:
+            return rgbx
+        out = rgbx.clone()
+        for b in range(rgbx.shape[0] // 2, rgbx.shape[0]):      # one launch per edited image
             ops.img_paste(rgbx[b], init_rgbx, pixel_mask, out=out[b])
         return out
 

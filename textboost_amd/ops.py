@@ -574,6 +574,28 @@ def dpm_step_blend(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sigma_t, 
             L.ptr(z0), L.ptr(noise), L.ptr(mask), hw, keep_a, keep_s)
 
 
+def invert_step(x, eps2, x2, traj_out, n_per_b, B, guidance, cx, ce):
+    """one guided DDIM-inversion step up the schedule (csrc/invert.hip): x = cx x + ce (e_u + g (e_c - e_u)), x2 = half(x) twice,
+    traj_out (fp32 [B, n_per_b] or None) = x."""
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == B * n_per_b
+    assert eps2.dtype == L.half_dtype() and x2.dtype == L.half_dtype() and eps2.is_contiguous() and x2.is_contiguous()
+    assert eps2.numel() == 2 * B * n_per_b and x2.numel() == 2 * B * n_per_b
+    assert traj_out is None or (traj_out.dtype == torch.float32 and traj_out.is_contiguous() and traj_out.numel() == B * n_per_b)
+    _launch("tb_invert_step", L.ptr(x), L.ptr(eps2), L.ptr(x2), L.ptr(traj_out), n_per_b, B, guidance, cx, ce)
+
+
+def dpm_step_pin(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sigma_t, ca, cb, cc, pin, n_src, mask, hw):
+    """`dpm_step`, then rows [0, n_src) and the cells of the other rows that `mask` leaves out take `pin` (csrc/invert.hip).
+    pin fp32 [n_per_b] (shared by the B rows), mask uint8 [hw] (non-zero = repaint; shared by channels and rows) or None: every cell."""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (x, m_prev, pin))
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == hw)
+    assert eps2.dtype == L.half_dtype() and x2.dtype == L.half_dtype() and eps2.is_contiguous() and x2.is_contiguous()
+    assert x.numel() == B * n_per_b and m_prev.numel() == B * n_per_b and pin.numel() == n_per_b
+    assert eps2.numel() == 2 * B * n_per_b and x2.numel() == 2 * B * n_per_b
+    _launch("tb_dpm_step_pin", L.ptr(x), L.ptr(eps2), L.ptr(m_prev), L.ptr(x2), n_per_b, B, guidance, alpha_t, sigma_t, ca, cb, cc,
+            L.ptr(pin), n_src, L.ptr(mask), hw)
+
+
 def img_paste(gen, orig, mask, out=None):
     """mask ? gen : orig per pixel: gen / orig int32 RGBX [H, W] (rows may be strided), mask uint8 [H, W] (non-zero = gen) -> int32 [H, W]"""
     h, w = gen.shape

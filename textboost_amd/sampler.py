@@ -11,6 +11,10 @@ Nothing here synchronises with the host, so the whole loop can be captured in a 
 
 `HipSampler.denoise_from` is the same loop started mid-schedule from the latents of an encoded photo (image editing, edit.py): with a mask the
 update and the per-step select of the kept cells are one launch as well (`tb_dpm_step_blend`), so editing launches what text-to-image does.
+
+`HipSampler.invert` walks an encoded photo UP the schedule (DDIM inversion, one `tb_invert_step` per level) and returns the trajectory;
+`denoise(p2p=..., pin=trajectory)` then keeps the source rows of a prompt-to-prompt edit on it (`tb_dpm_step_pin`), so the source image is
+the photo and the edited rows inherit its layout (inference.py --invert-image).
 """
 from __future__ import annotations
 
@@ -86,6 +90,22 @@ class DPMSolverPP2M:
     def noise_scalars(self, i: int) -> Tuple[float, float]:
         """(alpha, sigma) of `add_noise` at the start of step i: x_i = alpha z0 + sigma noise.  i = len(timesteps) (past the last step): (1, 0)."""
         return self.alpha_sigma(self.sigmas[i])
+
+    def inversion_scalars(self, k: int) -> Tuple[float, float]:
+        """(cx, ce) of the inversion step that takes x on level k+1 to level k = steps-1 .. 0 (level j is `noise_scalars(j)`, level `steps` the
+        clean latent) with the model evaluated at timesteps[k] ON THAT x -- DDIM inversion in the convention of the published
+        prompt-to-prompt / null-text code:  m = (x - sigma_{k+1} eps) / alpha_{k+1};  x_k = alpha_k m + sigma_k eps = cx x + ce eps.  For a
+        fixed eps this is the algebraic inverse of the solver's first-order step `coefficients(k, begin=k)` (and of the final step)."""
+        if self.prediction_type != "epsilon":
+            raise NotImplementedError(
+                f"inversion of a {self.prediction_type} model is not built: a v output would have to be converted to a noise prediction with the "
+                "scalars of the level its input is on, and in an inversion step the input is one level off the timestep the model is asked about "
+                "(SD1.x and SD2.1-base are epsilon models)")
+        if not 0 <= k < len(self.timesteps):
+            raise IndexError(f"inversion step {k}: the schedule has steps 0 .. {len(self.timesteps) - 1}")
+        a_k, s_k = self.noise_scalars(k)
+        a_n, s_n = self.noise_scalars(k + 1)
+        return a_k / a_n, s_k - a_k * s_n / a_n
 
     def coefficients(self, i: int, begin: int = 0) -> Tuple[float, float, float]:
         """x_next = ca x + cb m0 + cc m_prev  for step i  (m = data prediction).  begin: the first step that runs (image editing starts
@@ -180,7 +200,8 @@ class HipSampler:
         self.t_dev = [torch.full((2 * B,), t, dtype=torch.int64, device=dev) for t in self.timesteps]
         self.generator: Optional[torch.Generator] = None
 
-    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None, p2p=None):
+    def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None, p2p=None, pin=None,
+                pin_mask=None):
         """cond / uncond: fp16 or fp32 [B*77, D] text-encoder outputs.  Returns the final latents fp32 [B,4,h,w].
         step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`.
         maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step.
@@ -189,26 +210,38 @@ class HipSampler:
         p2p: a `p2p.P2PControl` of this UNet (DPM-Solver++ only).  Rows [0, B/2) are then the source images and [B/2, B) the edited ones (the
         caller gives both halves the same latents); steps i < floor(cross_steps * steps) run the controlled cross-attention and steps
         i < floor(self_steps * steps) the controlled self-attention of the edited conditional rows, every other row stays plain.  Not with
-        `maps` (the recorder recomputes an uncontrolled softmax) or `regions` (both take over the edited rows' cross-attention): ValueError."""
+        `maps` (the recorder recomputes an uncontrolled softmax) or `regions` (both take over the edited rows' cross-attention): ValueError.
+        pin: fp32 [steps+1, 4, h, w], one photo's trajectory from `invert` (needs `p2p`; `latents` must be None).  All rows start from pin[0];
+        step i is one `tb_dpm_step_pin` launch that puts the source rows [0, B/2) on pin[i+1], so they end as pin[steps] = z0 exactly, while
+        the edited rows take the solver's step.  pin_mask: uint8 [h, w] (non-zero = repaint; needs `pin`): the edited rows' cells outside it
+        stay on the trajectory as well and end as z0.  Without `pin` the method launches what it launched before."""
         B, sch = self.B, self.sch
         p2p_cross, p2p_self = self._p2p_steps(p2p, maps, regions)
         region_steps = self._region_steps(regions, region_steps, self.steps)
+        pin, pin_mask = self._pin_args(pin, pin_mask, p2p, latents)
         if p2p is not None:
             p2p.reset()
         if maps is not None:
             maps.zero()
-        if latents is None:
-            latents = torch.randn(self.x.shape, device=self.x.device, generator=self.generator)
-        self.x.copy_(latents * sch.init_noise_sigma)
+        if pin is not None:
+            self.x.copy_(pin[0].expand_as(self.x))
+        else:
+            if latents is None:
+                latents = torch.randn(self.x.shape, device=self.x.device, generator=self.generator)
+            self.x.copy_(latents * sch.init_noise_sigma)
         self.m_prev.zero_()
         self.x2[:B].copy_(self.x)
         self.x2[B:].copy_(self.x)
         ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
         n = self.x[0].numel()
+        hw = self.x.shape[2] * self.x.shape[3]
         for i in range(self.steps):
             eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None, p2p, i < p2p_cross, i < p2p_self)
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i)
+            if pin is not None:
+                ops.dpm_step_pin(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc, pin[i + 1], B // 2, pin_mask, hw)
+                continue
             if getattr(sch, "needs_noise", False):  # the variance noise of the ancestral step rides in the m_prev operand
                 if step_noise is not None:
                     self.m_prev.copy_(step_noise[i])
@@ -216,6 +249,59 @@ class HipSampler:
                     self.m_prev.normal_(generator=self.generator)
             ops.dpm_step(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc)
         return self.x
+
+    def invert(self, cond_ehs, uncond_ehs, z0, guidance: float = 1.0):
+        """DDIM inversion of encoded photos: z0 fp32 [B, 4, h, w], or [1, 4, h, w] / [4, h, w] shared by the B rows -> the
+        trajectory fp32 [steps+1, B, 4, h, w] (a new tensor): traj[steps] = z0, traj[k] = the latents on level k (`noise_scalars(k)`), traj[0]
+        the noise `denoise` starts from.  Step k = steps-1 .. 0 evaluates the UNet at timesteps[k] on the latents of level k+1 and applies
+        `DPMSolverPP2M.inversion_scalars(k)` in one `tb_invert_step` launch: `steps` UNet forwards, `steps` launches, no host synchronisation
+        (capturable).  cond / uncond describe the photo; guidance 1 is the conditional prediction alone, the usual choice for inversion.
+        DPM-Solver++ on an epsilon model only; every refusal comes before anything is touched."""
+        B, sch, steps = self.B, self.sch, self.steps
+        if not isinstance(sch, DPMSolverPP2M):
+            raise NotImplementedError(f"inversion runs on the DPM-Solver++ scheduler only, not on {type(sch).__name__}")
+        scalars = [sch.inversion_scalars(k) for k in range(steps)]          # (v-prediction: NotImplementedError)
+        g = float(guidance)
+        if not (math.isfinite(g) and g >= 0.0):
+            raise ValueError(f"inversion guidance {guidance}: a finite number >= 0")
+        if not torch.is_tensor(z0) or z0.dtype != torch.float32:
+            raise ValueError(f"z0 {getattr(z0, 'dtype', type(z0).__name__)}: expected an fp32 tensor")
+        shape = tuple(self.x.shape)
+        if tuple(z0.shape) not in (shape, (1,) + shape[1:], shape[1:]):
+            raise ValueError(f"z0 {tuple(z0.shape)}: the sampler is built for {shape} (or one {shape[1:]} shared by the rows)")
+        traj = torch.empty((steps + 1,) + shape, dtype=torch.float32, device=self.x.device)
+        traj[steps].copy_(z0.to(self.x.device).reshape((-1,) + shape[1:]).expand(shape))
+        self.x.copy_(traj[steps])
+        self.x2[:B].copy_(self.x)
+        self.x2[B:].copy_(self.x)
+        ehs = torch.cat([uncond_ehs, cond_ehs]).to(L.half_dtype()).contiguous()
+        n = self.x[0].numel()
+        for k in range(steps - 1, -1, -1):
+            eps2 = self.unet.forward(self.x2, self.t_dev[k], ehs)
+            cx, ce = scalars[k]
+            ops.invert_step(self.x, eps2, self.x2, traj[k], n, B, g, cx, ce)
+        return traj
+
+    def _pin_args(self, pin, pin_mask, p2p, latents):
+        """`denoise(pin=..., pin_mask=...)`: every refusal, before anything is touched.  -> (pin, pin_mask) on the device, contiguous"""
+        if pin is None:
+            if pin_mask is not None:
+                raise ValueError("pin_mask without pin: the mask says which cells of the edited rows leave the pinned trajectory")
+            return None, None
+        if p2p is None:
+            raise ValueError("pin without p2p: the pinned rows are the source rows of a prompt-to-prompt edit")
+        if latents is not None:
+            raise ValueError("pin with latents: every row starts from pin[0], the noise the photo inverts to")
+        want = (self.steps + 1,) + tuple(self.x.shape[1:])
+        if not torch.is_tensor(pin) or pin.dtype != torch.float32 or tuple(pin.shape) != want:
+            raise ValueError(f"pin {getattr(pin, 'dtype', type(pin).__name__)} {tuple(getattr(pin, 'shape', ()))}: expected float32 {want}, one "
+                             "photo's trajectory (`invert(...)[:, b]`)")
+        if pin_mask is not None and (not torch.is_tensor(pin_mask) or pin_mask.dtype != torch.uint8 or
+                                     tuple(pin_mask.shape) != tuple(self.x.shape[2:])):
+            raise ValueError(f"pin_mask {getattr(pin_mask, 'dtype', type(pin_mask).__name__)} {tuple(getattr(pin_mask, 'shape', ()))}: expected "
+                             f"uint8 {tuple(self.x.shape[2:])}")
+        pin = pin.to(self.x.device).contiguous()
+        return pin, (None if pin_mask is None else pin_mask.to(self.x.device).contiguous())
 
     def denoise_from(self, cond_ehs, uncond_ehs, z0, noise, strength, mask=None, maps=None, regions=None, region_steps=None):
         """Image editing: diffusers' StableDiffusionImg2ImgPipeline and, with a mask, the latent blend of StableDiffusionInpaintPipeline for a
