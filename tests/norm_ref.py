@@ -42,6 +42,30 @@ value added first), a tree level is a stage of length 2.  k = sum(L - 1) + 4 (th
            6 butterfly levels, 16 wave totals sequentially.
   f32      gn_f32_*_kernel (mean first): ceil(HW gs / 256) per thread, 6 butterfly levels, 4 wave totals.
   ln       ln_fwd/bwd_kernel (mean first, one wave per row): 8 * ceil(C / 8 / 64) per lane, 6 butterfly levels.
+
+THE LAYERNORMS THAT RIDE IN OTHER LAUNCHES (tests/test_gpu_fused_norm_scale.py); all mean first, on the 16-bit-ROUNDED row the launch writes:
+  epi      gemm8.hip, TB_ACT_LN_FWD / TB_ACT_LN_BWD epilogue of the row-spanning Linear tiles (N = 320): a thread adds the 8 values of its column
+           group sequentially (8), the C / 8 = 40 partials of a row go through the LDS to 8 reducer lanes that add C / 64 = 5 each sequentially (5),
+           then 3 xor-shuffle levels (2, 2, 2).  k = 7 + 4 + 3 + 4 = 18 at C = 320.  LN_BWD sums g and g xhat over the same structure (kb = k) and
+           reads (mean, rstd) as the preceding LN_FWD launch wrote them (k of this path).
+  chain    ff_chain.h ff_chain_layernorm (tb_chain320; tb_ff_fwd with pre_W): four threads per row, each adds its C / 4 = 80 values sequentially
+           (80), then 2 shuffle levels (2, 2).  k = 79 + 2 + 4 = 85 at C = 320.
+  ffbwd    ff_fused.hip, tb_ff_bwd with ln_x (backward sums only, kb): a lane adds its 10 x 4 = C / 8 accumulator values sequentially (40), 2 shuffle
+           levels (2, 2), one addition across the two waves of the row band (2).  kb = 39 + 3 + 4 = 46; (mean, rstd) are tb_ff_fwd's pre_stats (chain).
+
+THE FOLDED LAYERNORM (`fold_stages`, `fold_forward_bound`; one pass: var = Q / K - mean^2, clamped at zero).  Producer (gemm8.hip, rs_out): a thread adds
+the 8 rounded outputs of its column group and their squares sequentially (8), thread t < PR adds the tile's (tile width / 8) unit partials sequentially
+(tile width = C / slots) and writes slot tn; consumer (gemm8.hip rs_in: 8 + 8 slots; gemm.hip: 16, unused ones exact zeros): up to 16 slots added
+sequentially (16).  k = 7 + (C / slots / 8 - 1) + 15 + 4: 35 where the producers take 80-column tiles, 45 with 160-column tiles.
+  out = rstd (alpha acc - mean c1) + c2 (+ R),  acc = sum_k x_k W'_nk  (x: the written 16-bit row, W' = half(gamma (.) W), c1 = row sums of W', c2 = b + W beta:
+  the reference takes all of them AS THE KERNEL SEES THEM; the rounding of gamma (.) W is a stated divergence of the fold, not under test).
+  |out_kernel - out_ref| <= t_stat + t_acc + t_apply + t_round:
+  t_stat   |rstd (acc - mean c1)| e_r + rstd |c1| e_m, (e_m, e_r) = _stat_errors(row of width K, k, "onepass")
+  t_acc    rstd K u sum_k |x_k W'_nk|: the fp32 accumulation of acc (any order: at most K roundings at the magnitude of the absolute sum).  It is what
+           matters when |mean| / std is large: acc and mean c1 are both ~ |mean| |c1| and cancel to the size of the fluctuation.
+  t_apply  A u (rstd (|acc| + |mean c1|) + |c2| + |R|), A = 8: mean c1 (u), the subtraction (u), rsqrt + the product with rstd (3u), + c2 (u), + R (u), each
+           at most at the magnitude of the terms it combines
+  t_round  half an ulp of the output type at |out_ref| + the terms above.
 """
 import torch
 
@@ -194,6 +218,18 @@ def check(name, got, ref, bound, info=None, verbose=True):
     return w
 
 
+def sliced(rows, C, dtype, fill, sliced, device):
+    """a [rows, C] tensor, when `sliced` a column slice of a wider buffer whose margins hold `fill`.  Returns (view, buffer or None)."""
+    if not sliced:
+        return torch.full((rows, C), fill, device=device, dtype=dtype), None
+    buf = torch.full((rows, C + 24), fill, device=device, dtype=dtype)
+    return buf[:, 8:8 + C], buf
+
+
+def margins_untouched(buf, C, fill):
+    return buf is None or (bool((buf[:, :8] == fill).all()) and bool((buf[:, 8 + C:] == fill).all()))
+
+
 # ------------------------------------------------------------------------------------------------------------------ dispatch and k, from the structure
 def _cdiv(a, b):
     return (a + b - 1) // b
@@ -250,6 +286,15 @@ def path_stages(path, B, HW, C, G):
         return [_cdiv(HW * gs, 256)] + [2] * 6 + [4]
     if path == "ln":
         return [8 * _cdiv(C // 8, 64)] + [2] * 6
+    if path == "epi":
+        assert C % 64 == 0, C
+        return [8, C // 64, 2, 2, 2]
+    if path == "chain":
+        assert C % 4 == 0, C
+        return [C // 4, 2, 2]
+    if path == "ffbwd":
+        assert C % 8 == 0, C
+        return [C // 8, 2, 2, 2]
     raise ValueError(path)
 
 
@@ -259,6 +304,41 @@ def k_of(stages):
 
 def k_path(path, B, HW, C, G):
     return k_of(path_stages(path, B, HW, C, G))
+
+
+def fold_stages(C, slots):
+    """stage lengths of the folded LayerNorm's (sum, sum of squares) over a row of width C that the producers cut into `slots` column tiles"""
+    assert 1 <= slots <= 16 and C % (8 * slots) == 0, (C, slots)
+    return [8, C // slots // 8, 16]
+
+
+def fold_ref(x, Wp, c1, c2, R, eps):
+    """float64 value of the folded consumer's output [M, N] from the operands the kernel reads, (mean, rstd) [M], and the magnitudes the bound needs"""
+    X, W = x.double(), Wp.double()
+    mean = X.mean(1, keepdim=True)
+    var = ((X - mean) ** 2).mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    acc = X @ W.T
+    mc1 = mean * c1.double()[None, :]
+    out = rstd * (acc - mc1) + c2.double()[None, :] + (R.double() if R is not None else 0.0)
+    return out, (mean.reshape(-1), rstd.reshape(-1)), (acc, mc1, X.abs() @ W.abs().T)
+
+
+def fold_forward_bound(x, Wp, c1, c2, R, eps, k, out_dtype, parts=False):
+    """elementwise bound [M, N] on |kernel out - fold_ref out| (module docstring).  parts=True: also (e_m, rstd e_r) per row."""
+    M, K = x.shape
+    out, (mean, rstd), (acc, mc1, aabs) = fold_ref(x, Wp, c1, c2, R, eps)
+    c = _core(x, torch.ones(K, device=x.device), None, M, 1, K, 1, eps, False)
+    e_m, e_r = _stat_errors(c, eps, k, "onepass")
+    e_m, e_r, rs = e_m.reshape(M, 1), e_r.reshape(M, 1), rstd.reshape(M, 1)
+    t_stat = (rs * (acc - mc1)).abs() * e_r + rs * c1.double().abs()[None, :] * e_m
+    t_acc = rs * K * U * aabs
+    t_apply = A_APPLY * U * (rs * (acc.abs() + mc1.abs()) + c2.double().abs()[None, :] + (R.double().abs() if R is not None else 0.0))
+    e = t_stat + t_acc + t_apply
+    e = e + 0.5 * ulp(out.abs() + e, out_dtype)
+    if parts:
+        return e, (e_m.reshape(M), (rs * (e_r + 3 * U)).reshape(M))
+    return e
 
 
 def offset_ratio(k, xmax=4.0):
@@ -369,7 +449,15 @@ def gn_input(regime, B, HW, C, G, dtype, ratio=32, seed=11):
     return x.reshape(B * HW, C).to(dtype)
 
 
-def ln_input(regime, M, C, dtype, seed=13):
+def fold_offsets(k):
+    """LN_OFFSETS scaled so that the largest is what offset_ratio admits for a one-pass path with k additions"""
+    r = offset_ratio(k)
+    return tuple(o * r / 256.0 for o in LN_OFFSETS)
+
+
+def ln_input(regime, M, C, dtype, seed=13, offsets=None):
+    """x [M, C] of `dtype` (CPU), seeded.  offsets: |mean| / std per row of `offset`, cycled (default LN_OFFSETS; the one-pass fold: fold_offsets(k))"""
+    LN_OFFSETS = offsets or globals()["LN_OFFSETS"]
     x = torch.randn(M, C, generator=_gen(seed + M + C))
     if regime == UNIT:
         x = x * 1.5 + 0.2
@@ -379,7 +467,7 @@ def ln_input(regime, M, C, dtype, seed=13):
         x = x + torch.tensor([LN_OFFSETS[m % len(LN_OFFSETS)] for m in range(M)]).reshape(M, 1)
     elif regime == "mixed":
         for m in range(M):
-            s, o = _scale_offset(_KINDS[m % 4], 32.0, -1.0 if m & 4 else 1.0)
+            s, o = _scale_offset(_KINDS[m % 4], max(abs(v) for v in offsets) if offsets else 32.0, -1.0 if m & 4 else 1.0)    # (its offset rows: 32, or the path's cap)
             x[m] = x[m] * s + o
     elif regime == "degenerate":
         x[0] = 0.0

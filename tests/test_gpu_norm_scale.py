@@ -53,15 +53,10 @@ def _hname(dt):
 
 
 def _sliced(rows, C, dtype, fill, sliced):
-    """a [rows, C] tensor, in `offset` / `mixed` a column slice of a wider buffer whose margins hold `fill`.  Returns (view, buffer or None)."""
-    if not sliced:
-        return torch.full((rows, C), fill, device=dev, dtype=dtype), None
-    buf = torch.full((rows, C + 24), fill, device=dev, dtype=dtype)
-    return buf[:, 8:8 + C], buf
+    return R.sliced(rows, C, dtype, fill, sliced, dev)
 
 
-def _margins_untouched(buf, C, fill):
-    return buf is None or (bool((buf[:, :8] == fill).all()) and bool((buf[:, 8 + C:] == fill).all()))
+_margins_untouched = R.margins_untouched
 
 
 # ------------------------------------------------------------------------------------------------------------------ GroupNorm

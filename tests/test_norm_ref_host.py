@@ -362,3 +362,232 @@ def test_statistics_term_stays_within_two_output_ulps(case):
             i = int(t_stat.argmax())
             ts, zz = t_stat.reshape(-1)[i].item(), z.reshape(-1)[i]
             assert ts <= 2 * R.ulp(zz, half).item(), (case.id, regime, half, ts, zz.item())
+
+
+# ------------------------------------------------------------------------------------------------------------------ the LayerNorms fused into other launches
+FUSED_PATHS = ("epi", "chain")     # norm_ref.path_stages: the gemm8 LN_FWD / LN_BWD epilogue, the ff / chain320 stage
+FUSED_C, FUSED_M, FUSED_TILE = 320, 130, 64
+FUSED_MUTANTS = ["statistics of the un-rounded fp32 row", "statistics of row m^1", "statistics of row m + tile height", "LN_BWD with mean(g xhat) dropped"]
+
+
+def _fused_operands(regime, half, M=FUSED_M, C=FUSED_C):
+    """the fp32 row an epilogue holds before it rounds it (a sum of three operands: not representable in 16 bits), its LayerNorm parameters, dy, add"""
+    t32 = R.ln_input(regime, M, C, torch.float32)
+    gamma, beta = R.ln_params(regime, C)
+    g = torch.Generator().manual_seed(5)
+    dy, add = torch.randn(M, C, generator=g).to(half), torch.randn(M, C, generator=g).to(half)
+    return t32, gamma, beta, dy, add
+
+
+def fused_model(t32, gamma, beta, eps, stages, half, dy, add, mut=None):
+    """fp32 numpy model of sites 1 / 4 / 5 (forward) and 2 / 6 (backward): the row is rounded to the 16-bit type FIRST, the statistics are those of the
+    rounded row (mean, then centred squares, summed in the order of `stages`), y = (o - mean) rstd gamma + beta rounded; the backward reads o and the
+    forward's (mean, rstd): dx = rstd (g - mean g - xhat mean(g xhat)) + add, g = dy gamma.  Returns (o, y, dx) as torch tensors (o in `half`)."""
+    M, C = t32.shape
+    T = t32.numpy().astype(F32)
+    o = rnd(T, half)
+    ga, be = gamma.numpy().astype(F32), beta.numpy().astype(F32)
+    src = T if mut == "statistics of the un-rounded fp32 row" else o
+    n = F32(C)
+    mean = (staged_sum(src, stages) / n).astype(F32)
+    dl = (src - mean[:, None]).astype(F32)
+    var = (staged_sum((dl * dl).astype(F32), stages) / n).astype(F32)
+    rstd = (F32(1) / np.sqrt((var + F32(eps)).astype(F32))).astype(F32)
+    if mut == "statistics of row m^1":
+        idx = np.minimum(np.arange(M) ^ 1, M - 1)
+        mean, rstd = mean[idx], rstd[idx]
+    if mut == "statistics of row m + tile height":
+        idx = (np.arange(M) + FUSED_TILE) % M
+        mean, rstd = mean[idx], rstd[idx]
+    mu, rs = mean[:, None], rstd[:, None]
+    xh = ((o - mu).astype(F32) * rs).astype(F32)
+    y = ((xh * ga).astype(F32) + be).astype(F32)
+    g = (dy.float().numpy() * ga).astype(F32)
+    m1 = (staged_sum(g, stages) / n).astype(F32)[:, None]
+    m2 = (staged_sum((g * xh).astype(F32), stages) / n).astype(F32)[:, None]
+    if mut == "LN_BWD with mean(g xhat) dropped":
+        m2 = np.zeros_like(m2)
+    dx = ((rs * ((g - m1).astype(F32) - (xh * m2).astype(F32)).astype(F32)).astype(F32) + add.float().numpy()).astype(F32)
+    tt = lambda a: torch.from_numpy(rnd(a, half)).double()
+    return torch.from_numpy(o).to(half), tt(y), tt(dx)
+
+
+def _check_fused_model(path, regime, eps, half, mut=None):
+    t32, gamma, beta, dy, add = _fused_operands(regime, half)
+    stages = R.path_stages(path, FUSED_M, 1, FUSED_C, 1)
+    k = R.k_of(stages)
+    o, y, dx = fused_model(t32, gamma, beta, eps, stages, half, dy, add, mut)
+    yr, _, dxr = R.layernorm_ref(o, gamma, beta, eps, dy, add)
+    name = f"model fused {path} {regime} eps {eps:g} {half}{' [' + mut + ']' if mut else ''}"
+    w = R.check(name + " y", y, yr, R.layernorm_forward_bound(o, gamma, beta, eps, k, half), verbose=False)
+    return max(w, R.check(name + " dx", dx, dxr, R.layernorm_backward_bound(o, dy, add, gamma, eps, k, half), verbose=False))
+
+
+@pytest.mark.parametrize("path", FUSED_PATHS)
+def test_fused_layernorm_models_stay_inside_the_bound(path):
+    assert int(np.prod(R.path_stages(path, 1, 1, FUSED_C, 1))) >= FUSED_C
+    worst = 0.0
+    for regime in R.REGIMES:
+        for eps in R.REGIME_EPS[regime]:
+            for half in (torch.float16, torch.bfloat16):
+                worst = max(worst, _check_fused_model(path, regime, eps, half))
+    print(f"[norm-bound] fused path {path}: stages {R.path_stages(path, 1, 1, FUSED_C, 1)}, k = {R.k_path(path, 1, 1, FUSED_C, 1)}, "
+          f"offsets |mean| / std {R.LN_OFFSETS}, worst model error / bound {worst:.3f}")
+    assert worst <= 1.0
+
+
+def test_every_fused_site_mutant_is_rejected_by_some_regime(capsys):
+    table = {m: [] for m in FUSED_MUTANTS}
+    for regime in R.REGIMES:
+        for eps in R.REGIME_EPS[regime]:
+            for path in FUSED_PATHS:
+                for mut in FUSED_MUTANTS:
+                    try:
+                        _check_fused_model(path, regime, eps, torch.float16, mut)
+                    except AssertionError:
+                        table[mut].append(f"{regime}/{eps:g}/{path}")
+    with capsys.disabled():
+        print("\n[mutants] fused LayerNorm sites, rejected by (regime/eps/path):")
+        for mut in FUSED_MUTANTS:
+            print(f"[mutants]   {mut:46s} {', '.join(table[mut]) or '-- NOWHERE --'}")
+    missing = [m for m in FUSED_MUTANTS if not table[m]]
+    assert not missing, f"no regime rejects: {missing}"
+
+
+@pytest.mark.parametrize("path", FUSED_PATHS)
+def test_statistics_term_of_the_fused_paths_stays_within_two_output_ulps(path):
+    """the cap of test_statistics_term_stays_within_two_output_ulps as a checked condition for the mean-first paths of the fused sites, on the LayerNorm
+    regimes (|mean| / std up to 256): the statistics term at the element where it is largest is within 2 ulps of the 16-bit output there"""
+    M, C = FUSED_M, FUSED_C
+    k = R.k_path(path, M, 1, C, 1)
+    for regime in R.REGIMES:
+        eps = R.REGIME_EPS[regime][0]
+        for half in (torch.float16, torch.bfloat16):
+            x = R.ln_input(regime, M, C, half)
+            gamma, beta = R.ln_params(regime, C)
+            _, t_stat, _ = R.layernorm_forward_bound(x, gamma, beta, eps, k, half, parts=True)
+            z, _, _ = R.layernorm_ref(x, gamma, beta, eps)
+            X = x.double()
+            const = (X.amax(1, keepdim=True) == X.amin(1, keepdim=True)).expand_as(X)     # (the constant rows of `degenerate`: exempt as above)
+            t_stat = torch.where(const, torch.zeros_like(t_stat), t_stat)
+            i = int(t_stat.argmax())
+            ts, zz = t_stat.reshape(-1)[i].item(), z.reshape(-1)[i]
+            assert ts <= 2 * R.ulp(zz, half).item(), (path, regime, half, ts, zz.item())
+
+
+# ------------------------------------------------------------------------------------------------------------------ the folded LayerNorm (site 3)
+FOLD_MUTANTS = ["c1 summed from the un-rounded gamma W", "mean c1 term dropped", "c2 without W beta", "a slot too few summed", "fold: statistics of row m^1",
+                "fold: eps dropped"]
+FOLD_CASES = [(320, 4), (640, 4), (1280, 16)]     # (C, slots): 80-, 160- and 80-column producer tiles
+
+
+def _fold_data(regime, Cw, slots, half, M=24, N=48):
+    k = R.k_of(R.fold_stages(Cw, slots))
+    x = R.ln_input(regime, M, Cw, half, offsets=R.fold_offsets(k))
+    gamma, beta = R.ln_params(regime, Cw)
+    g = torch.Generator().manual_seed(41)
+    W = torch.randn(N, Cw, generator=g) / Cw ** 0.5
+    b = torch.randn(N, generator=g) * 0.3
+    return k, x, gamma, beta, W, b
+
+
+def fold_model(x, W, gamma, beta, b, eps, slots, half, mut=None):
+    """fp32 numpy model of the fold: W' = half(gamma W), c1 = row sums of W', c2 = b + W beta; the producer's per-tile (sum, sum of squares) of the 16-bit
+    row, 8 values per unit and the units of a tile sequentially; the consumer adds the slots sequentially; var = Q / K - mean^2 clamped at zero;
+    out = rstd (acc - mean c1) + c2 with the cancellation in fp32.  Returns (out float64 of the rounded result, W', c1, c2 as the reference takes them)."""
+    M, K = x.shape
+    X = x.float().numpy()
+    gW = (W.numpy().astype(F32) * gamma.numpy().astype(F32)[None, :]).astype(F32)
+    Wp = rnd(gW, half)
+    c1 = Wp.sum(1, dtype=F32)
+    c2 = ((W.numpy().astype(F32) @ beta.numpy().astype(F32)).astype(F32) + b.numpy().astype(F32)).astype(F32)
+    c1_k = gW.sum(1, dtype=F32) if mut == "c1 summed from the un-rounded gamma W" else c1
+    c2_k = b.numpy().astype(F32) if mut == "c2 without W beta" else c2
+    tw = K // slots
+    xs = X.reshape(M, slots, tw)
+    S = staged_sum(xs, [8, tw // 8])
+    Q = staged_sum((xs * xs).astype(F32), [8, tw // 8])
+    n_sum = slots - 1 if mut == "a slot too few summed" else slots
+    sx, sq = staged_sum(S[:, :n_sum], [n_sum]), staged_sum(Q[:, :n_sum], [n_sum])
+    inv_k = F32(1) / F32(K)
+    mean = (sx * inv_k).astype(F32)
+    var = np.maximum(((sq * inv_k).astype(F32) - (mean * mean).astype(F32)).astype(F32), F32(0))
+    with np.errstate(divide="ignore"):
+        rstd = (F32(1) / np.sqrt((var + F32(0.0 if mut == "fold: eps dropped" else eps)).astype(F32))).astype(F32)
+    if mut == "fold: statistics of row m^1":
+        idx = np.arange(M) ^ 1
+        mean, rstd = mean[idx], rstd[idx]
+    acc = (X @ Wp.T).astype(F32)
+    mc1 = np.zeros_like(acc) if mut == "mean c1 term dropped" else (mean[:, None] * c1_k[None, :]).astype(F32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = ((rstd[:, None] * (acc - mc1).astype(F32)).astype(F32) + c2_k[None, :]).astype(F32)
+    t = torch.from_numpy
+    return t(rnd(out, half)).double(), t(Wp).to(half), t(c1), t(c2)
+
+
+def _check_fold_model(Cw, slots, regime, eps, half, mut=None):
+    k, x, gamma, beta, W, b = _fold_data(regime, Cw, slots, half)
+    out, Wp, c1, c2 = fold_model(x, W, gamma, beta, b, eps, slots, half, mut)
+    ref, _, _ = R.fold_ref(x, Wp, c1, c2, None, eps)
+    return R.check(f"model fold C {Cw} slots {slots} {regime} eps {eps:g} {half}{' [' + mut + ']' if mut else ''}", out, ref,
+                   R.fold_forward_bound(x, Wp, c1, c2, None, eps, k, half), verbose=False)
+
+
+@pytest.mark.parametrize("Cw,slots", FOLD_CASES)
+def test_fold_model_stays_inside_the_bound_at_the_chosen_offset_ratio(Cw, slots):
+    """the reference alone -- the fp32 model -- stays within fold_forward_bound at the |mean| / std that offset_ratio admits for the path's k"""
+    k = R.k_of(R.fold_stages(Cw, slots))
+    worst = 0.0
+    for regime in R.REGIMES:
+        for eps in R.REGIME_EPS[regime]:
+            for half in (torch.float16, torch.bfloat16):
+                worst = max(worst, _check_fold_model(Cw, slots, regime, eps, half))
+    print(f"[norm-bound] fold C {Cw}: stages {R.fold_stages(Cw, slots)}, k = {k}, offset ratio {R.offset_ratio(k)} (|mean| / std per row "
+          f"{R.fold_offsets(k)}), worst model error / bound {worst:.3f}")
+    assert worst <= 1.0 and R.offset_ratio(k) < 256
+
+
+def test_every_fold_mutant_is_rejected_by_some_regime(capsys):
+    table = {m: [] for m in FOLD_MUTANTS}
+    for regime in R.REGIMES:
+        for eps in R.REGIME_EPS[regime]:
+            for Cw, slots in FOLD_CASES[1:]:
+                for mut in FOLD_MUTANTS:
+                    # (both half types: the rounding of gamma W that the c1 mutant leaves out is 8 times larger in bfloat16, and under the worst-case
+                    # accumulation term K u sum |x W'| only that one shows it)
+                    for half, hn in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
+                        try:
+                            _check_fold_model(Cw, slots, regime, eps, half, mut)
+                        except AssertionError:
+                            table[mut].append(f"{regime}/{eps:g}/C{Cw}/{hn}")
+    with capsys.disabled():
+        print("\n[mutants] folded LayerNorm, rejected by (regime/eps/width/half type):")
+        for mut in FOLD_MUTANTS:
+            print(f"[mutants]   {mut:46s} {', '.join(table[mut][:8]) or '-- NOWHERE --'}{' ... (%d)' % len(table[mut]) if len(table[mut]) > 8 else ''}")
+    missing = [m for m in FOLD_MUTANTS if not table[m]]
+    assert not missing, f"no regime rejects: {missing}"
+
+
+@pytest.mark.parametrize("Cw,slots", FOLD_CASES)
+def test_statistics_term_of_the_fold_stays_within_two_output_ulps(Cw, slots):
+    """the cap for the one-pass fold, on the normalised row it stands for: with the offsets of fold_offsets(k) the statistics term of the one-pass
+    forward bound is within 2 ulps of the 16-bit normalised value; the next power of two would break offset_ratio's condition"""
+    k = R.k_of(R.fold_stages(Cw, slots))
+    r = R.offset_ratio(k)
+    assert r in (2, 4, 8, 16, 32)
+    if r < 32:
+        assert 0.5 * k * R.U * (3 * (2 * r) ** 2 + 1) + k * R.U * (2 * r + 0.8) / 4.0 > 2.0 ** -10
+    M = 24
+    for regime in R.REGIMES:
+        eps = R.REGIME_EPS[regime][0]
+        for half in (torch.float16, torch.bfloat16):
+            x = R.ln_input(regime, M, Cw, half, offsets=R.fold_offsets(k))
+            gamma, beta = R.ln_params(regime, Cw)
+            _, t_stat, _ = R.forward_bound(x, gamma, beta, M, 1, Cw, 1, eps, False, k, half, "onepass", parts=True)
+            z, _, _ = R.layernorm_ref(x, gamma, beta, eps)
+            X = x.double()
+            const = (X.amax(1, keepdim=True) == X.amin(1, keepdim=True)).expand_as(X)
+            t_stat = torch.where(const, torch.zeros_like(t_stat), t_stat)
+            i = int(t_stat.argmax())
+            ts, zz = t_stat.reshape(-1)[i].item(), z.reshape(-1)[i]
+            assert ts <= 2 * R.ulp(zz, half).item(), (Cw, regime, half, ts, zz.item())

@@ -93,6 +93,9 @@ __device__ __forceinline__ void gelu_erf_both_f(float x, float& g, float& dg) { 
 }
 __device__ __forceinline__ float quick_gelu_f(float x) { return x / (1.f + __expf(-1.702f * x)); }
 __device__ __forceinline__ float quick_gelu_grad_f(float x) {
+  // (bfloat16 pre-activations past 2e38: 1.702 x overflows, and inf * (1 - s) = inf * 0 was NaN.  Beyond |x| = 62 the result is exactly 0 or 1;
+  // the clamp sits above every finite fp16 value, so nothing below it changes a bit.)
+  x = __builtin_amdgcn_fmed3f(x, -65536.f, 65536.f);
   float s = 1.f / (1.f + __expf(-1.702f * x));
   return s * (1.f + 1.702f * x * (1.f - s));
 }
