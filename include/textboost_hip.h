@@ -666,6 +666,39 @@ int tb_attn_loss_bwd(const tb_attn_desc* d, int dtype, const float* tok_w, const
 /* out[0] = norm * (sum of the n_slots * slot_floats partials, in double, in a fixed order): state[TB_ST_LOSS_ATTN] with norm = 1 / (B * n_slots) */
 int tb_attn_loss_final(const float* ws, int n_slots, int64_t slot_floats, float norm, float* out, tb_stream_t stream);
 
+/* ---- Attend-and-Excite (csrc/excite.hip; inference.py --excite) -------------------------------------------------------
+ * Per image, with A fp32 [nb, T, h * w] (the layout of tb_attn_token_maps: the mean over the supervised layers and their heads), last[b] the
+ * position of the first end-of-text token and words int32 [nb, n_words, n_pos] the token positions of every word (-1 padded):
+ *   pt_j[s] = softmax over j in [1, last) of 100 A[j][s]       M_w[s] = sum_{j in J_w} pt_j[s]       G_w = M_w * 3 x 3 Gaussian (sigma 0.5,
+ *   1-D taps [e^-2, 1, e^-2] / (1 + 2 e^-2), reflect padding)       l_w = max(0, 1 - max_s G_w[s])       L = max_w l_w
+ * Ties go to the lowest word index and the lowest position.  A word without a position is skipped.
+ *
+ * tb_excite_loss: loss[b] = L, word[b] = the worst word (-1: no word has a position), sel[b][0..9) = the positions whose taps feed the
+ * arg-max of that word, reflect-folded to unique positions in ascending order, -1 padded (all -1 when L = 0), and
+ *   dA[b][i][j] = loss_scale * dL/dA[j][sel_i] = -100 loss_scale kappa(sel_i) pt_j[sel_i] ([j in J_w*] - M_w*[sel_i])     j in [1, last)
+ * fp32 [nb, 9, T], zero elsewhere; kappa = the summed taps that fold onto the position.  One workgroup per image, fixed-order reductions in
+ * double, each output rounded once, no atomics: a relaunch is bit-identical.  2 <= T <= 128, h, w >= 2, h * w <= 2048, 1 <= n_words <= 8,
+ * 1 <= n_pos <= 16, loss_scale > 0.  check = 1 reads `last` and `words` back first (one small copy behind the stream's queued work; not
+ * inside a stream capture) and refuses a last outside [1, T] and a position that is neither -1 nor in [1, last); check = 0 reads nothing
+ * back, and the kernel ignores such a position.  Every refusal returns -22 and launches nothing. */
+int tb_excite_loss(const float* A, const int32_t* last, const int32_t* words, int nb, int T, int h, int w, int n_words, int n_pos,
+                   float loss_scale, int check, float* loss, int32_t* word, int32_t* sel, float* dA, tb_stream_t stream);
+/* tb_excite_bwd: reads B, H, Sq, Skv, hd, scale, Q / ldq, K / ldk and dQ / lddq of the descriptor (as tb_attn_loss_bwd).  For the images
+ * [b0, b0 + nb), every selected position s = sel[b - b0][i] >= 0 and every head it recomputes that query row's softmax p and ADDS
+ *   scale sum_j ds_j k_j,   ds_j = p_j (coef dA_j - sum_i p_i coef dA_i),   dA = dA[b - b0][i][0..Skv)   (so T of tb_excite_loss == Skv)
+ * to that row of dQ in the operand dtype as rounded(float(old) + add), coef = 1 / (supervised layers * H).  Rows that are not selected,
+ * images whose sel is all -1 and elements whose addend is zero are not written (-0 stays -0); dK is not touched.  One wave owns one
+ * (image, position, head) row slice, no atomics: a relaunch on the same inputs is bit-identical.  dtype TB_F16 only; hd % 8 == 0,
+ * hd <= 160, 1 <= Skv <= 128, any Sq, any leading dimension >= H * hd and any row alignment; anything else returns -22 and launches nothing. */
+int tb_excite_bwd(const tb_attn_desc* d, int dtype, int b0, int nb, const int32_t* sel, const float* dA, float coef, tb_stream_t stream);
+/* tb_excite_update: x fp32 [B, n_per_b] (the sampler's latents), g [B, n_per_b] in the library's 16-bit type (the gradient of loss_scale * L,
+ * the conditional rows of the UNet batch), step fp32 [B] on the device, x2 16-bit [2B, n_per_b] (tb_dpm_step's doubled copy), bad int32 [B].
+ * Two launches: bad[b] = (step[b] != 0 and some element of g[b] is inf or NaN); then, for the images with step[b] != 0 and bad[b] == 0,
+ *   x[b] = x[b] - (step[b] / loss_scale) * g[b]    (fp32, no fused multiply-add)      x2 = 16-bit (x | x)
+ * Every other image is not written at all: no image is half-updated. */
+int tb_excite_update(float* x, const void* g, const float* step, void* x2, int32_t* bad, int64_t n_per_b, int B, float loss_scale,
+                     tb_stream_t stream);
+
 /* ---- CLIP ViT patch embedding (csrc/clip_vision.hip; the image tower of the CLIP-T / CLIP-I evaluation, textboost_amd/clip_score.py) -------
  * img: B resident RGBX images of S x S pixels, image b at img + b * img_stride, rows row_stride pixels apart.  P = (S / patch)^2 patches.
  * w: TB_F16 [D][ldw], K = 4 patch^2 columns in the order (ky, kx, R G B X) then zeros up to Kp (a multiple of 32): the conv weight with

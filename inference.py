@@ -8,6 +8,7 @@ textboost_amd/generate.py.
         [--region "WORDS=x0,y0,x1,y1" | --region "WORDS=@mask.png" ...] [--region-steps F]
         [--edit-prompt TEXT] [--reweight WORD=F ...] [--cross-steps F] [--self-steps F]
         [--invert-image photo.jpg [--invert-guidance G] [--mask mask.png [--no-paste]]]
+        [--excite WORD [WORD ...] [--excite-steps F] [--excite-scale S] [--excite-loss-scale V] [--no-excite-refine]]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -68,6 +69,17 @@ prepared photo on top and the edit below (without --output: `<prompt>_inv.jpg` a
 --mask FILE (the photo's size, white = repaint) keeps the latent cells outside it on the photo's trajectory in the edited row as well, and the
 photo's bytes are pasted outside the mask (--no-paste writes the plain decode).  --reweight, --cross-steps, --self-steps, --with work as with
 --edit-prompt.  Not with --init-image, --strength, --region, --attn-map, --mask auto:WORD or --dilate, and not on a v-prediction model.
+
+--excite WORD [WORD ...] keeps every named subject in the image (textboost_amd/excite.py; Attend-and-Excite, Chefer et al.
+2023): `--with out/cat --prompt "a <dog> dog and a <cat> cat" --excite "<dog>" "<cat>"`.  During the first --excite-steps F of the steps
+(default 0.5) every step first nudges the latents down the gradient of a loss on the 16 x 16 cross-attention maps (the level-2 maps: a quarter
+of the latent side) until every word owns at least one strongly attended patch, with the step size --excite-scale S (default 20) times
+sqrt(1 - 0.5 i / (steps - 1)); at the steps 0, floor(0.2 steps) and floor(0.4 steps) the nudge repeats, at most 20 times, until each image's
+loss is below 0.05 / 0.5 / 0.8 (--no-excite-refine: one nudge per step).  The 16-bit backward carries the loss times --excite-loss-scale V
+(default 256).  Words resolve as for --attn-map; at most 8 words of at most 16 token positions each.  `<output stem>_excite.json` reports,
+per guided step and seed, the loss before (and, at the refinement steps, after) the nudges, the worst word, the number of nudges and the
+updates skipped because the gradient was not finite.  Works with --with (its main use); not with --region, --edit-prompt, --reweight,
+--invert-image, --init-image, --mask or --attn-map.  The defaults are the paper's; they have not been measured on pretrained weights here.
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
@@ -130,7 +142,90 @@ def build_parser():
                    help="with --edit-prompt / --reweight: edit this photo; --prompt describes it, the photo is inverted to noise first")
     p.add_argument("--invert-guidance", dest="invert_guidance", type=float, default=None, metavar="G",
                    help="with --invert-image: guidance scale of the inversion, finite and >= 0 (default 1)")
+    p.add_argument("--excite", dest="excite", type=str, nargs="+", default=None, metavar="WORD",
+                   help="Attend-and-Excite: nudge the latents during the first steps until each of these words of the prompt owns a strongly "
+                        "attended patch (at most 8 words)")
+    p.add_argument("--excite-steps", dest="excite_steps", type=float, default=None, metavar="F",
+                   help="with --excite: the guidance acts on the first floor(F * steps) steps, 0 <= F <= 1 (default 0.5)")
+    p.add_argument("--excite-scale", dest="excite_scale", type=float, default=None, metavar="S",
+                   help="with --excite: the step size factor, > 0 (default 20)")
+    p.add_argument("--excite-loss-scale", dest="excite_loss_scale", type=float, default=None, metavar="V",
+                   help="with --excite: the factor the 16-bit backward carries the loss with, > 0 (default 256)")
+    p.add_argument("--no-excite-refine", dest="no_excite_refine", action="store_true",
+                   help="with --excite: no iterative refinement at the steps 0, floor(0.2 steps), floor(0.4 steps)")
     return p
+
+
+def check_excite_flags(args):
+    """--excite and its companions: the refusals that need no file, by flag name.  -> is the generation guided?"""
+    from textboost_amd import excite as X
+    if not args.excite:
+        for flag, given in (("--excite-steps", args.excite_steps is not None), ("--excite-scale", args.excite_scale is not None),
+                            ("--excite-loss-scale", args.excite_loss_scale is not None), ("--no-excite-refine", args.no_excite_refine)):
+            if given:
+                raise SystemExit(f"inference.py: {flag} needs --excite WORD [WORD ...] (the words it keeps in the image)")
+        return False
+    why = {"--region": "the excite pass moves the latents by the unmasked attention, which the regions then contradict; pin the words with "
+                       "--region or excite them, not both",
+           "--edit-prompt": "the prompt-to-prompt rows share their latents, which the excite pass would move apart",
+           "--reweight": "the prompt-to-prompt rows share their latents, which the excite pass would move apart",
+           "--invert-image": "the source row is pinned to the photo's trajectory, which the excite pass would leave",
+           "--init-image": "the excite pass is built for a generation from noise, not for the partial schedule of an edited photo",
+           "--mask": "a mask belongs to --init-image / --invert-image, which --excite does not go with",
+           "--attn-map": "the recorded maps would mix the guided steps' attention with the excite pass's own forwards; run --attn-map without "
+                         "--excite"}
+    for flag, given in (("--region", bool(args.region)), ("--edit-prompt", args.edit_prompt is not None), ("--reweight", bool(args.reweight)),
+                        ("--invert-image", args.invert_image is not None), ("--init-image", args.init_image is not None),
+                        ("--mask", args.mask is not None), ("--attn-map", args.attn_map is not None)):
+        if given:
+            raise SystemExit(f"inference.py: --excite does not go with {flag}: {why[flag]}")
+    if len(args.excite) > X.MAX_WORDS:
+        raise SystemExit(f"inference.py: --excite takes at most {X.MAX_WORDS} words, not {len(args.excite)}")
+    try:
+        if args.excite_steps is not None:
+            X.guided_steps(args.excite_steps, args.steps)
+    except X.ExciteError as e:
+        raise SystemExit(f"inference.py: {e}")
+    import math
+    for flag, v in (("--excite-scale", args.excite_scale), ("--excite-loss-scale", args.excite_loss_scale)):
+        if v is not None and not (math.isfinite(v) and v > 0.0):
+            raise SystemExit(f"inference.py: {flag} {v}: a finite number > 0")
+    return True
+
+
+def check_excite_args(args, run):
+    """--excite: the words' token positions, on the host, before any model is built.  -> None or {"words", "positions", "last", options}"""
+    from textboost_amd import excite as X
+    if not check_excite_flags(args):
+        return None
+    from textboost_amd.attn_maps import run_tokenizer, token_positions
+    try:
+        tokenizer = run_tokenizer(args.model, run)
+    except OSError as e:
+        raise SystemExit(f"inference.py: --excite: {e} (--model must be a local diffusers model directory)")
+    T = model_text_len(args.model)
+    positions = []
+    for w in args.excite:
+        try:
+            positions.append(token_positions(tokenizer, args.prompt, w, T))
+        except ValueError as e:
+            raise SystemExit(f"inference.py: --excite: {e}")
+    ids = list(tokenizer(args.prompt, truncation=True, padding="max_length", max_length=T).input_ids)
+    last = X.first_eos(ids, tokenizer.eos_token_id)
+    try:
+        X.word_table(positions, last)
+    except X.ExciteError as e:
+        raise SystemExit(f"inference.py: {e}")
+    return {"words": list(args.excite), "positions": positions, "last": last,
+            "steps": X.EXCITE_STEPS if args.excite_steps is None else args.excite_steps,
+            "scale": X.SCALE if args.excite_scale is None else args.excite_scale,
+            "loss_scale": X.LOSS_SCALE if args.excite_loss_scale is None else args.excite_loss_scale,
+            "refine": not args.no_excite_refine}
+
+
+def excite_path(args):
+    stem = os.path.splitext(args.output)[0] if args.output is not None else args.prompt.replace(" ", "_")
+    return stem + "_excite.json"
 
 
 def load_runs(args):
@@ -169,7 +264,8 @@ def load_runs(args):
         for what, text in [("--prompt", args.prompt)] + [("--attn-map", w) for w in (args.attn_map or [])] + \
                 [("--region", r) for r in (getattr(args, "region", None) or [])] + \
                 [("--edit-prompt", t) for t in [getattr(args, "edit_prompt", None)] if t is not None] + \
-                [("--reweight", r) for r in (getattr(args, "reweight", None) or [])]:
+                [("--reweight", r) for r in (getattr(args, "reweight", None) or [])] + \
+                [("--excite", w) for w in (getattr(args, "excite", None) or [])]:
             if tok in text:
                 raise SystemExit(f"inference.py: {what} {text!r} uses {tok}, which both {first[tok]} and {dropped} hold: ambiguous (the first "
                                  "run's vector would be taken); rename the token in one run or leave it out of the prompt")
@@ -439,6 +535,7 @@ def main(argv=None):
     if not args.model:
         raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
     G.check_model_dir(args.model, "inference.py")
+    check_excite_flags(args)
     check_invert_flags(args)
     check_p2p_flags(args)
     run = load_runs(args)
@@ -449,6 +546,7 @@ def main(argv=None):
     region = check_region_args(args, run, edit)
     p2p = check_p2p_args(args, run)
     invert = check_invert_args(args)
+    excite = check_excite_args(args, run)
     seeds = args.seeds
     if invert is not None:
         seeds = ["inv"]        # one photo, one deterministic edit: the file names carry `inv` in the seed's place
@@ -513,6 +611,15 @@ def main(argv=None):
                     pixel_mask = torch.from_numpy(np.ascontiguousarray(pm)).to(pipe.dev)
             rgbx = pipe.invert_edit_images(states[1], states[0], z0, ctl, invert_guidance=invert["guidance"], latent_mask=latent_mask,
                                            pixel_mask=pixel_mask, init_rgbx=init_rgbx if pixel_mask is not None else None, what=what)
+        elif excite is not None:      # Attend-and-Excite (textboost_amd/excite.py): every refusal has happened on the host already
+            import json
+            from textboost_amd.excite import ExciteControl
+            xctl = ExciteControl(pipe.unet, excite["positions"], excite["last"], words=excite["words"], excite_steps=excite["steps"],
+                                 scale=excite["scale"], loss_scale=excite["loss_scale"], refine=excite["refine"])
+            rgbx = pipe.images(states[1], states[0], latents, what=what + f", excite {excite['words']}", excite=xctl)
+            with open(excite_path(args), "w") as f:
+                json.dump(dict(xctl.report(), prompt=args.prompt, seeds=list(seeds)), f, indent=1)
+            print(f"wrote {excite_path(args)}: {len(xctl.trace)} guided step(s), {xctl.skipped} skipped update(s)")
         elif edit is None:
             rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps, p2p=ctl)
         else:       # a seed's latent is the noise of its image; the photo is encoded once

@@ -408,12 +408,13 @@ class Pipeline:
         """the UNet of one trained run: its K/V adapters folded in, or the base weights"""
         self.set_unet_adapters([(run.unet_lora, run.unet_rank, 1.0)] if run.unet_rank else [])
 
-    def images(self, cond, uncond, latents, what: str = "", maps=None, regions=None, region_steps=None, p2p=None) -> torch.Tensor:
+    def images(self, cond, uncond, latents, what: str = "", maps=None, regions=None, region_steps=None, p2p=None, excite=None) -> torch.Tensor:
         """text states fp32 [B*T, D] twice, latents fp32 [B, 4, size, size] on the device -> int32 RGBX [B, 8 size, 8 size] (resident).
         Non-finite final latents raise before anything is decoded.  maps: an `attn_maps.AttnMapRecorder` of `self.unet` (the images do not
         change with it).  regions / region_steps: a `regions.RegionSet` of `self.unet` and how many steps it acts on (`HipSampler.denoise`).
-        p2p: a `p2p.P2PControl` of `self.unet`: rows [0, B/2) are the source images, [B/2, B) the edited ones."""
-        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps, regions=regions, region_steps=region_steps, p2p=p2p)
+        p2p: a `p2p.P2PControl` of `self.unet`: rows [0, B/2) are the source images, [B/2, B) the edited ones.
+        excite: an `excite.ExciteControl` of `self.unet` (Attend-and-Excite; its trace is filled by the call)."""
+        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps, regions=regions, region_steps=region_steps, p2p=p2p, excite=excite)
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         return self.vae.decode_rgbx(x)

@@ -706,6 +706,52 @@ def attn_loss_final(ws, norm, out):
     _launch("tb_attn_loss_final", L.ptr(ws), ws.shape[0], ws.shape[1], norm, L.ptr(out))
 
 
+EXCITE_SEL = 9   # selected positions per image (csrc/excite.hip)
+
+
+def excite_loss(A, last, words, h, w, loss_scale, loss, word, sel, dA, check=False):
+    """The Attend-and-Excite loss of every image (csrc/excite.hip): A fp32 [nb, T, h * w] (the accumulator of
+    `attn_token_maps`), last int32 [nb], words int32 [nb, n_words, n_pos] (-1 padded) -> loss fp32 [nb], word int32 [nb], sel int32 [nb, 9]
+    (-1 padded) and dA fp32 [nb, 9, T] = loss_scale * dL/dA at the selected positions.  check: read the tables back and validate them first."""
+    nb, T, HW = A.shape
+    assert HW == h * w and A.dtype == torch.float32 and A.is_contiguous()
+    assert words.dim() == 3 and words.shape[0] == nb and words.dtype == torch.int32 and words.is_contiguous()
+    assert last.dtype == torch.int32 and last.is_contiguous() and last.numel() == nb
+    assert loss.dtype == torch.float32 and loss.is_contiguous() and loss.numel() == nb
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (word, sel)) and word.numel() == nb and sel.numel() == nb * EXCITE_SEL
+    assert dA.dtype == torch.float32 and dA.is_contiguous() and dA.numel() == nb * EXCITE_SEL * T
+    _launch("tb_excite_loss", L.ptr(A), L.ptr(last), L.ptr(words), nb, T, h, w, words.shape[1], words.shape[2], loss_scale, int(check),
+            L.ptr(loss), L.ptr(word), L.ptr(sel), L.ptr(dA))
+
+
+def excite_bwd(q, k, dq, sel, dA, B, H, Sq, Skv, hd, coef, b0=0, nb=None, scale=None):
+    """ADDS the gradient of the Attend-and-Excite loss to the selected rows of dq [B*Sq, H*hd] for the images [b0, b0 + nb) (csrc/excite.hip):
+    q, dq [B*Sq, H*hd], k [B*Skv, H*hd] in the library's half type (column slices allowed), sel int32 [nb, 9], dA fp32 [nb, 9, Skv],
+    coef = 1 / (supervised layers * H)."""
+    nb = B - b0 if nb is None else nb
+    assert q.dtype == k.dtype == dq.dtype and all(t.stride(1) == 1 for t in (q, k, dq))
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == nb * EXCITE_SEL, (tuple(sel.shape), nb)
+    assert dA.dtype == torch.float32 and dA.is_contiguous() and dA.numel() == nb * EXCITE_SEL * Skv, (tuple(dA.shape), nb, Skv)
+    d = L.AttnDesc()
+    d.B, d.H, d.Sq, d.Skv, d.hd, d.causal, d.scale = B, H, Sq, Skv, hd, 0, scale if scale is not None else hd ** -0.5
+    d.Q, d.ldq = L.ptr(q), q.stride(0)
+    d.K, d.ldk = L.ptr(k), k.stride(0)
+    d.dQ, d.lddq = L.ptr(dq), dq.stride(0)
+    with _rec("excite_bwd_kernel", 4.0 * nb * EXCITE_SEL * H * Skv * hd):
+        _launch("tb_excite_bwd", d, _dt(q), b0, nb, L.ptr(sel), L.ptr(dA), coef)
+
+
+def excite_update(x, g, step, x2, bad, loss_scale):
+    """x[b] -= (step[b] / loss_scale) * g[b] for the images whose g is finite (bad[b] = 1 and no write otherwise), x2 = 16-bit (x | x):
+    x fp32 [B, ...], g the library's half type of that shape, step fp32 [B], x2 half [2B, ...], bad int32 [B] (csrc/excite.hip)."""
+    B = x.shape[0]
+    n = x.numel() // B
+    assert x.dtype == torch.float32 and x.is_contiguous() and step.dtype == torch.float32 and step.is_contiguous() and step.numel() == B
+    assert g.dtype == L.half_dtype() and x2.dtype == L.half_dtype() and g.is_contiguous() and x2.is_contiguous()
+    assert g.numel() == B * n and x2.numel() == 2 * B * n and bad.dtype == torch.int32 and bad.is_contiguous() and bad.numel() == B
+    _launch("tb_excite_update", L.ptr(x), L.ptr(g), L.ptr(step), L.ptr(x2), L.ptr(bad), n, B, loss_scale)
+
+
 def kpl_cos(h, h0, dh, partial, loss_out, loss_scale, weight):
     M, D = h.shape
     _launch("tb_kpl_cos", L.ptr(h), h.stride(0), L.ptr(h0), h0.stride(0), _dt(h0), L.ptr(dh), dh.stride(0) if dh is not None else 0,

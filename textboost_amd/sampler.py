@@ -201,7 +201,7 @@ class HipSampler:
         self.generator: Optional[torch.Generator] = None
 
     def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None, p2p=None, pin=None,
-                pin_mask=None):
+                pin_mask=None, excite=None):
         """cond / uncond: fp16 or fp32 [B*77, D] text-encoder outputs.  Returns the final latents fp32 [B,4,h,w].
         step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`.
         maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step.
@@ -214,8 +214,17 @@ class HipSampler:
         pin: fp32 [steps+1, 4, h, w], one photo's trajectory from `invert` (needs `p2p`; `latents` must be None).  All rows start from pin[0];
         step i is one `tb_dpm_step_pin` launch that puts the source rows [0, B/2) on pin[i+1], so they end as pin[steps] = z0 exactly, while
         the edited rows take the solver's step.  pin_mask: uint8 [h, w] (non-zero = repaint; needs `pin`): the edited rows' cells outside it
-        stay on the trajectory as well and end as z0.  Without `pin` the method launches what it launched before."""
+        stay on the trajectory as well and end as z0.  Without `pin` the method launches what it launched before.
+        excite: an `excite.ExciteControl` of this UNet (Attend-and-Excite; both schedulers: it acts before the step).  Every step
+        i < floor(excite_steps * steps) first runs the excite pass on the current latents -- a truncated UNet forward of the usual
+        (uncond | cond) batch, `excite_loss`, `backward_sample`, `excite_update` with step scale * sqrt(1 - 0.5 i / (steps - 1)) -- and then the
+        unchanged guided step.  At the steps {0, floor(0.2 steps), floor(0.4 steps)} (unless refine is off) the pass repeats, at most max_refine
+        times, until every image's loss is below {0.05, 0.5, 0.8}: the one place where the host reads the [B] losses; an image already
+        below gets step 0.  A non-finite gradient skips that image's update and is counted in `excite.skipped`, never raised.
+        `excite.trace` holds one entry per guided step.  Not with `maps`, `regions`, `p2p` or `pin`: ValueError.  Without `excite` the method
+        launches what it launched before."""
         B, sch = self.B, self.sch
+        ex_steps = self._excite_steps(excite, maps, regions, p2p, pin)
         p2p_cross, p2p_self = self._p2p_steps(p2p, maps, regions)
         region_steps = self._region_steps(regions, region_steps, self.steps)
         pin, pin_mask = self._pin_args(pin, pin_mask, p2p, latents)
@@ -236,6 +245,8 @@ class HipSampler:
         n = self.x[0].numel()
         hw = self.x.shape[2] * self.x.shape[3]
         for i in range(self.steps):
+            if i < ex_steps:
+                self._excite_pass(i, ehs, excite)
             eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None, p2p, i < p2p_cross, i < p2p_self)
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i)
@@ -248,7 +259,89 @@ class HipSampler:
                 else:
                     self.m_prev.normal_(generator=self.generator)
             ops.dpm_step(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc)
+        if ex_steps:
+            self._excite_finish(excite)
         return self.x
+
+    # ------------------------------------------------------------------ Attend-and-Excite (excite.py)
+    def _excite_steps(self, excite, maps, regions, p2p, pin):
+        """how many steps of `denoise` run the excite pass; every refusal, before anything is touched.  Writes the control's tables into the
+        UNet's (enable_excite() on first use)."""
+        if excite is None:
+            return 0
+        from .excite import guided_steps
+        for name, given in (("maps", maps), ("regions", regions), ("p2p", p2p), ("pin", pin)):
+            if given is not None:
+                raise ValueError(f"Attend-and-Excite does not go with {name}: the excite pass runs its own forward of the UNet and moves the "
+                                 f"latents between the steps, which {name} does not account for")
+        unet = self.unet
+        if excite.n != self.B or excite.T != unet.T or (excite.h, excite.w) != (unet.H, unet.W):
+            raise ValueError(f"the excite control is built for {excite.n} images, {excite.T} tokens and a {excite.h} x {excite.w} grid; the sampler "
+                             f"runs {self.B} images, {unet.T} tokens, {unet.H} x {unet.W}")
+        if unet.excite is None:
+            unet.enable_excite()
+        ex = unet.excite
+        if (ex.b0, ex.nb) != (self.B, self.B) or tuple(ex.words.shape) != tuple(excite.table.shape):
+            raise ValueError(f"the UNet's excite buffers hold rows [{ex.b0}, {ex.b0 + ex.nb}) and a {tuple(ex.words.shape)} word table; the "
+                             f"sampler needs rows [{self.B}, {2 * self.B}) and {tuple(excite.table.shape)}")
+        ex.words.copy_(excite.table)
+        ex.last.copy_(excite.last)
+        if getattr(self, "_ex_step", None) is None:
+            self._ex_step = torch.zeros(self.B, device=self.x.device)
+            self._ex_bad = torch.zeros(self.B, dtype=torch.int32, device=self.x.device)
+        excite.trace, excite.skipped = [], 0
+        self._ex_pending = []
+        return guided_steps(excite.excite_steps, self.steps)
+
+    def _excite_pass(self, i, ehs, ctl):
+        """the excite pass of step i on the current latents (x, x2), in front of the guided step"""
+        from .excite import refine_thresholds, step_size
+        unet, B = self.unet, self.B
+        ex = unet.excite
+        base = step_size(ctl.scale, i, self.steps)
+        thr = refine_thresholds(self.steps).get(i) if ctl.refine else None
+        entry = dict(step=i, step_size=base, threshold=thr, iterations=1, loss_before=None, loss_after=None, word=None, skipped=0)
+        ctl.trace.append(entry)
+
+        def evaluate():
+            unet.forward(self.x2, self.t_dev[i], ehs, until="excite")
+            unet.excite_loss(ctl.loss_scale)
+
+        def update():
+            g = unet.backward_sample()[B:]
+            ops.excite_update(self.x, g, self._ex_step, self.x2, self._ex_bad, ctl.loss_scale)
+            self._ex_pending.append((entry, "skipped", self._ex_bad.clone()))
+
+        evaluate()
+        if thr is None:   # nothing is read back: the figures of the trace are collected behind the last step
+            self._ex_pending.append((entry, "loss_before", ex.loss.clone()))
+            self._ex_pending.append((entry, "word", ex.word.clone()))
+            self._ex_step.fill_(base)
+            update()
+            return
+        k = 0
+        while True:
+            losses = ex.loss.tolist()
+            if k == 0:
+                entry["loss_before"], entry["word"] = losses, ex.word.tolist()
+            entry["loss_after"], entry["iterations"] = losses, k
+            if k == ctl.max_refine or all(l < thr for l in losses):
+                return
+            self._ex_step.copy_(torch.tensor([base if l >= thr else 0.0 for l in losses], dtype=torch.float32))
+            update()
+            k += 1
+            evaluate()
+
+    def _excite_finish(self, ctl):
+        """one read-back behind the last step: the losses, worst words and skipped updates the guided steps left on the device"""
+        for entry, key, t in self._ex_pending:
+            v = t.tolist()
+            if key == "skipped":
+                entry["skipped"] += int(sum(v))
+                ctl.skipped += int(sum(v))
+            else:
+                entry[key] = v
+        self._ex_pending = []
 
     def invert(self, cond_ehs, uncond_ehs, z0, guidance: float = 1.0):
         """DDIM inversion of encoded photos: z0 fp32 [B, 4, h, w], or [1, 4, h, w] / [4, h, w] shared by the B rows -> the

@@ -78,6 +78,12 @@ def pack_conv3x3(w, dev, dtype=None):
     return fwd, dg
 
 
+def pack_conv4_dgrad(w):
+    """conv_in.weight [C0, 4, 3, 3] -> fp32 [4][9][C0], tb_conv_to4's pack of the convolution that is conv_in's input gradient: the NHWC
+    gradient [.., C0] convolved with the flipped taps, W'[ci][ky * 3 + kx][co] = w[co][ci][2 - ky][2 - kx]."""
+    return w.flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], 9, w.shape[0]).contiguous()
+
+
 def pack_linear(w, dev, dtype=None):
     w = _f16(w, dtype).to(dev)
     if w.dim() == 4:  # 1x1 conv
@@ -115,6 +121,8 @@ class HipUNet:
         self.regions = None     # a regions.RegionSet: every cross-attention forward then runs the region-masked kernel with that level's table (opt-in; None = the plain forward)
         self.p2p = None         # a p2p.P2PControl: extra launches overwrite the edited conditional rows of the attention outputs (opt-in; None = the plain forward, launch for launch)
         self.attn_loss = None   # enable_attn_loss(): the cross-attention localisation loss in the backward of the supervised layers (None = no launch)
+        self.excite = None      # enable_excite(): Attend-and-Excite -- forward(until="excite") / backward_sample() record and inject (None = no launch)
+        self._bwd_through = False   # backward_sample(): the backward does not stop at the first cross-attention
         self._bufs: Dict[str, torch.Tensor] = {}
         self.tape: List = []
         self._pack(state_dict)
@@ -167,6 +175,47 @@ class HipUNet:
         """out[0] = L_attn of the last backward (unscaled; the mean over the batch and the supervised layers)"""
         al = self.attn_loss
         ops.attn_loss_final(al.ws, 1.0 / (self.B * al.n), out)
+
+    # ------------------------------------------------------------------ Attend-and-Excite (DESIGN.md section 22)
+    EXCITE_LEVEL = 2   # the supervised maps: (H >> 2) x (W >> 2), the 16 x 16 maps of 64 x 64 latents
+
+    def enable_excite(self, rows: Optional[Tuple[int, int]] = None, n_words: int = 8, n_pos: int = 16):
+        """--excite: the cross-attention layers whose map lies on level 2 are supervised by the Attend-and-Excite loss (csrc/excite.hip).  With
+        `excite.record` set, their forward adds the head-and-layer mean of their probabilities for the images `rows` = [b0, b1) (default: the
+        second half, the conditional rows of a guided call) to `excite.acc` fp32 [nb, T, h_l * w_l]; with `excite.inject` set, their backward
+        adds the gradient of the loss (`ops.excite_bwd`) to dq.  `forward(until="excite")` and `backward_sample()` set both.  Static inputs,
+        to be written by the caller: `excite.words` int32 [nb, n_words, n_pos] (-1 until then) and `excite.last` int32 [nb].  `excite_loss()`
+        fills loss / word / sel / dA.  Every buffer is allocated here."""
+        if self.dtype == torch.float32:
+            raise NotImplementedError("Attend-and-Excite has 16-bit kernels only (an fp32 UNet has no excite pass)")
+        lvl = self.EXCITE_LEVEL
+        layers = [p for p, _ in self.xattn if self.xattn_level[p] == lvl]
+        if not layers:
+            raise ValueError(f"Attend-and-Excite supervises the cross-attention maps of level {lvl}; this UNet has cross-attention on levels "
+                             f"{sorted(set(self.xattn_level.values()))} only")
+        b0, b1 = rows if rows is not None else (self.B // 2, self.B)
+        if not (0 <= b0 < b1 <= self.B):
+            raise ValueError(f"rows {(b0, b1)} are not a range of the UNet's batch of {self.B}")
+        h, w = self.H >> lvl, self.W >> lvl
+        if h < 2 or w < 2:
+            raise ValueError(f"the level-{lvl} map is {h} x {w}: the 3 x 3 Gaussian with reflect padding needs at least 2 x 2")
+        nb, dev = b1 - b0, self.dev
+        ex = SimpleNamespace(level=lvl, layers=set(layers), last_layer=layers[-1], n=len(layers), b0=b0, nb=nb, h=h, w=w, record=False, inject=False)
+        ex.acc = torch.zeros(nb, self.T, h * w, device=dev)
+        ex.words = torch.full((nb, n_words, n_pos), -1, dtype=torch.int32, device=dev)
+        ex.last = torch.full((nb,), 2, dtype=torch.int32, device=dev)
+        ex.loss = torch.zeros(nb, device=dev)
+        ex.word = torch.full((nb,), -1, dtype=torch.int32, device=dev)
+        ex.sel = torch.full((nb, ops.EXCITE_SEL), -1, dtype=torch.int32, device=dev)
+        ex.dA = torch.zeros(nb, ops.EXCITE_SEL, self.T, device=dev)
+        self.excite = ex
+        return ex
+
+    def excite_loss(self, loss_scale: float = 1.0, check: bool = False):
+        """the loss of the recorded maps -> excite.loss / word / sel / dA (dA = loss_scale * dL/dA); nothing is read back unless `check`"""
+        ex = self.excite
+        ops.excite_loss(ex.acc, ex.last, ex.words, ex.h, ex.w, loss_scale, ex.loss, ex.word, ex.sel, ex.dA, check=check)
+        return ex.loss
 
     # ------------------------------------------------------------------ cross-attention K/V adapters (SURVEY 8(f).4)
     def enable_kv_lora(self, r: int, alpha: Optional[float] = None, seed: Optional[int] = None):
@@ -257,6 +306,8 @@ class HipUNet:
         w = _f32v(sd["conv_in.weight"], dev)                     # [C0,4,3,3]
         P["conv_in.wp"] = w.permute(2, 3, 1, 0).reshape(36, ch[0]).contiguous()
         P["conv_in.b"] = _f32v(sd["conv_in.bias"], dev)
+        # conv_in's input gradient (backward_sample) is a 3x3 C0 -> 4 convolution of the NHWC gradient with flipped taps: tb_conv_to4's [4][9][C] pack
+        P["conv_in.wd4"] = pack_conv4_dgrad(w)
         w = _f32v(sd["conv_out.weight"], dev)                    # [4,C0,3,3]
         P["conv_out.wp"] = w.permute(0, 2, 3, 1).reshape(4, 9, ch[0]).contiguous()
         P["conv_out.wdp"] = w.permute(2, 3, 0, 1).reshape(36, ch[0]).contiguous()
@@ -539,6 +590,9 @@ class HipUNet:
             ops.attention_dual_fwd(q2[src], k2[ksrc], pv1, None if pv2 is None else q2[edt], k2[kedt], pv2, o2[edt], n, heads, HW, T, T, hd)
         if self.attn_maps is not None:
             self.attn_maps.record(q2, k2, heads, lvl_hw, hd)
+        ex = self.excite
+        if ex is not None and ex.record and (tb + ".attn2") in ex.layers:   # Attend-and-Excite: the mean over the supervised layers and heads
+            ops.attn_token_maps(q2, k2, ex.acc, B, heads, HW, T, hd, b0=ex.b0, nb=ex.nb, w=1.0 / (heads * ex.n), accumulate=True)
         t2 = self.buf(prefix + ".t2", M, C)
         # --- GEGLU feed-forward
         ls3 = self.buf(prefix + ".ls3", M, 2, torch.float32)
@@ -610,7 +664,10 @@ class HipUNet:
                     al.coef_done.add(level)
                 ops.attn_loss_bwd(q2, k2, dq2, dk2, self.attn_tok_w, al.g[level], B, heads, HW, T, hd, al.coef, al.loss_scale, al.ws,
                                   al.slot[tb + ".attn2"])
-            if stop_after_cross:
+            ex = self.excite
+            if ex is not None and ex.inject and (tb + ".attn2") in ex.layers:   # Attend-and-Excite: its gradient joins the selected rows of dq2
+                ops.excite_bwd(q2, k2, dq2, ex.sel, ex.dA, B, heads, HW, T, hd, 1.0 / (heads * ex.n), b0=ex.b0, nb=ex.nb)
+            if stop_after_cross and not self._bwd_through:
                 return
             dt1 = self.scratch("g4", M, C)
             if fuse_ln:
@@ -659,10 +716,28 @@ class HipUNet:
         else:
             ops.gemm(ehs16, P["kv_all.w"], self.kv_all)
 
-    def forward(self, sample, timesteps, ehs16, ehs_ready=None):
+    def forward(self, sample, timesteps, ehs16, ehs_ready=None, until=None):
         """ehs_ready: optional callable run ONCE per forward, right before the first kernel that reads `ehs16` (the hoisted K/V projection, in front
         of the first cross-attention; at the end of the forward at the latest): a stream join when the caller produces `ehs16` on another stream
-        while the layers in front of it already run, or the producer itself (the trainer issues the text-encoder forward from it)."""
+        while the layers in front of it already run, or the producer itself (the trainer issues the text-encoder forward from it).
+        until="excite" (after enable_excite()): the Attend-and-Excite pass -- the supervised layers record into `excite.acc` (zeroed here) and the
+        forward returns None behind the last of them; `_saved` then holds the truncated tape `backward_sample()` walks.  With `excite.record`
+        set by the caller a full forward records as well."""
+        if until is not None:
+            if until != "excite":
+                raise ValueError(f"until={until!r}: only \"excite\" is built")
+            if self.excite is None:
+                raise RuntimeError("forward(until=\"excite\") needs enable_excite()")
+            self.excite.record = True
+            try:
+                return self._forward(sample, timesteps, ehs16, ehs_ready, cut=self.excite.last_layer)
+            finally:
+                self.excite.record = False
+        return self._forward(sample, timesteps, ehs16, ehs_ready)
+
+    def _forward(self, sample, timesteps, ehs16, ehs_ready=None, cut=None):
+        if self.excite is not None and self.excite.record:
+            self.excite.acc.zero_()
         geo, B, P = self.geo, self.B, self.P
         ch = geo.block_out_channels
         nl = len(ch)
@@ -769,6 +844,12 @@ class HipUNet:
                     tbwd, _ = self._transformer(f"up_blocks.{i}.attentions.{j}", mid, dst, hw[lvl], lvl, x_partials=pk)
                     up_records.append(("res", rb, cb, mid, (i, j)))
                     up_records.append(("attn", tbwd, mid, dst, None))
+                    if cut is not None and cut == f"up_blocks.{i}.attentions.{j}.transformer_blocks.0.attn2":
+                        # the excite pass ends here: nothing behind the last supervised layer reaches the loss
+                        self._saved = dict(truncated=True, tail=dst, cats=cats, cat_views=cat_views, down=down_records, mid=mid_records,
+                                           up=up_records, hw=hw, Ms=Ms, ehs16=ehs16)
+                        self._ensure_kv()
+                        return None
                 else:
                     rb, _ = self._resnet(f"up_blocks.{i}.resnets.{j}", cb, dst, hw[lvl])
                     up_records.append(("res", rb, cb, dst, (i, j)))
@@ -927,3 +1008,120 @@ class HipUNet:
             ops.gemm_f32_t(dt, ehs, gA, n2r, Dc, M, a_trans=True, w_trans=True, R=gA)
             ops.gemm_f32_t(dt, self.kv_lora_A.view(n2r, Dc), d_ehs_out, M, Dc, n2r, w_trans=True, R=d_ehs_out)
         return d_ehs_out
+
+    # ------------------------------------------------------------------ backward to the input (dgrad only, down to d_sample)
+    def backward_sample(self, dpred=None, excite=None):
+        """The gradient with respect to `sample`, 16-bit [B, 4, H, W] (a buffer of this executor): the dgrad chain of `backward` run THROUGH the
+        first cross-attention, its transformer block, down_blocks.0.resnets.0 and conv_in (tb_conv_to4 on the flipped-tap pack); the d_ehs
+        GEMM is not run.  dpred fp32 [B, 4, H, W] after a full forward: the general gradient of sum(pred * dpred).  dpred = None after
+        forward(until="excite"): the truncated tape is walked from a zero gradient, and the only source is the Attend-and-Excite gradient that
+        `ops.excite_bwd` adds to dq in the supervised layers (`excite`, default: dpred is None; the selection of the last `excite_loss()`).
+        A skip tensor whose consumer was never recorded has no gradient: nothing is added for it."""
+        if self.dtype == torch.float32:
+            raise NotImplementedError("backward_sample has 16-bit kernels only")
+        S, geo, B, P = self._saved, self.geo, self.B, self.P
+        truncated = bool(S.get("truncated", False))
+        inject = (dpred is None) if excite is None else bool(excite)
+        if inject and self.excite is None:
+            raise RuntimeError("backward_sample: the Attend-and-Excite gradient needs enable_excite()")
+        if truncated and dpred is not None:
+            raise ValueError("backward_sample(dpred) needs a full forward: the last one was truncated (until=\"excite\")")
+        if not truncated and dpred is None:
+            raise ValueError("backward_sample() without dpred walks the truncated tape of forward(until=\"excite\"); after a full forward pass dpred")
+        if self.attn_loss is not None:
+            self.attn_loss.coef_done.clear()
+        ch = geo.block_out_channels
+        nl = len(ch)
+        hw, Ms = S["hw"], S["Ms"]
+        L_ = geo.layers_per_block
+        self._bwd_through = True
+        if self.excite is not None:
+            self.excite.inject = inject
+        try:
+            if truncated:
+                tail = S["tail"]
+                g = self.buf("grad.excite.tail", tail.shape[0], tail.shape[1])
+                g.zero_()
+            else:
+                da = self.scratch("g1", Ms[0], ch[0])
+                ops.conv4_to_nhwc(dpred, P["conv_out.wdp"], None, da, B, self.H, self.W, ch[0], sign=-1)
+                g = self.buf("grad.final", Ms[0], ch[0])
+                self._gn_bwd(da, S["final"], "conv_norm_out", S["sto"], g, hw[0][0] * hw[0][1], True)
+            dcat = {}
+            for kind, fn, xin, xout, tag in reversed(S["up"]):
+                M, cin = xin.shape
+                if kind == "up":
+                    name, lvl = fn
+                    gx = self.buf(f"grad.up.{name}", M, cin)
+                    if (name + ".wdsub") in P:
+                        ops.gemm(g, P[name + ".wdsub"], gx,
+                                 conv=dict(B=B, Hin=hw[lvl - 1][0], Win=hw[lvl - 1][1], Cin=g.shape[1], Hout=hw[lvl][0], Wout=hw[lvl][1], stride=1,
+                                           sign=1, upsample=3, transposed=0))
+                    else:
+                        du = self.scratch("gu", Ms[lvl - 1], xin.shape[1])
+                        self._conv(g, name, du, B, hw[lvl - 1][0], hw[lvl - 1][1], hw[lvl - 1][0], hw[lvl - 1][1], dgrad=True)
+                        ops.pool2x2_sum(du, gx, B, hw[lvl][0], hw[lvl][1], cin)
+                    g = gx
+                elif kind == "attn":
+                    gx = self.buf(f"grad.attn.{M}x{cin}.u", M, cin)
+                    fn(g, gx)
+                    g = gx
+                else:
+                    i, j = tag
+                    gx = self.buf(f"grad.cat.{i}.{j}", M, cin)
+                    fn(g, gx)
+                    dcat[(i, j)] = gx
+                    g = gx[:, :S["cats"][(i, j)][1]]
+            for mi, (fn, xin, xout) in reversed(list(enumerate(S["mid"]))):
+                gx = self.buf(f"grad.mid.{mi}", xin.shape[0], xin.shape[1])
+                fn(g, gx)
+                g = gx
+            # skip gradient views by skip number: only of the concat buffers whose resnet was recorded
+            sk = list(range(len(self.skip_chs)))
+            skip_grad = {}
+            for i in range(nl):
+                for j in range(L_ + 1):
+                    k = sk.pop()
+                    if (i, j) in dcat:
+                        skip_grad[k] = dcat[(i, j)][:, S["cats"][(i, j)][1]:]
+            recs = list(reversed(S["down"]))
+            premerged = False
+            for ri, (kind, fn, xin, xout, s_idx) in enumerate(recs):
+                if s_idx is not None and not premerged and s_idx in skip_grad:
+                    merged = self.buf(f"grad.skipmerge.{s_idx}", xout.shape[0], xout.shape[1])
+                    ops.add_f16(g, skip_grad[s_idx], merged)
+                    g = merged
+                premerged = False
+                if kind == "attn":
+                    gx = self.buf(f"grad.attn.{xin.shape[0]}x{xin.shape[1]}.d", xin.shape[0], xin.shape[1])
+                    fn[0](g, gx)
+                    g = gx
+                elif kind == "res":
+                    gx = self.buf(f"grad.res.{xin.shape[0]}x{xin.shape[1]}.d", xin.shape[0], xin.shape[1])
+                    fn(g, gx)
+                    g = gx
+                else:
+                    name, lvl = fn
+                    gx = self.buf(f"grad.down.{lvl}", xin.shape[0], xin.shape[1])
+                    nxt = recs[ri + 1][4] if ri + 1 < len(recs) else None
+                    R = skip_grad.get(nxt) if nxt is not None else None
+                    if (name + ".wdsub2") in P:
+                        ops.gemm(g, P[name + ".wdsub2"], gx, R=R,
+                                 conv=dict(B=B, Hin=hw[lvl + 1][0], Win=hw[lvl + 1][1], Cin=g.shape[1], Hout=hw[lvl][0], Wout=hw[lvl][1], stride=1,
+                                           sign=1, upsample=2, transposed=0))
+                    else:
+                        self._conv(g, name, gx, B, hw[lvl + 1][0], hw[lvl + 1][1], hw[lvl][0], hw[lvl][1], dgrad=True, transposed=1, R=R)
+                    premerged = R is not None
+                    g = gx
+            # g = d(conv_in output) along the down path; the output is skip tensor 0 as well (read by the last up-path resnet)
+            if 0 in skip_grad:
+                merged = self.buf("grad.skipmerge.0", g.shape[0], g.shape[1])
+                ops.add_f16(g, skip_grad[0], merged)
+                g = merged
+            d_sample = self.buf("d_sample", B * 4, self.H * self.W).view(B, 4, self.H, self.W)
+            ops.conv_to4(g, P["conv_in.wd4"], None, d_sample, B, self.H, self.W, ch[0])
+            return d_sample
+        finally:
+            self._bwd_through = False
+            if self.excite is not None:
+                self.excite.inject = False
