@@ -699,6 +699,33 @@ int tb_excite_bwd(const tb_attn_desc* d, int dtype, int b0, int nb, const int32_
 int tb_excite_update(float* x, const void* g, const float* step, void* x2, int32_t* bad, int64_t n_per_b, int B, float loss_scale,
                      tb_stream_t stream);
 
+/* ---- prompt-to-prompt LocalBlend (csrc/local_blend.hip; inference.py --blend, textboost_amd/local_blend.py, HipSampler.denoise(blend=...);
+ * DESIGN 23) ----
+ * A prompt-to-prompt generation of n pairs (sampler rows [0, n) source, [n, 2n) edited).  acc fp32 [2n, T, hl * wl]: the accumulator of
+ * tb_attn_token_maps for the conditional rows c_src | c_edit (rows j and n + j belong to pair j).  words int32 [2n, n_pos]: every row's
+ * word positions in ITS prompt, -1 padded; a position outside [0, T) is ignored.  Per row r:
+ *   m_r[s] = sum over the table, in table order, of acc[r][p][s] (fp32 adds)      P_r = 3 x 3 max of m_r, stride 1, windows clipped at the
+ *   borders      mx_r = max_s m_r[s]      bit_r[s] = P_r[s] > fl32(th * mx_r)  (one rounded multiply, strict compare; an empty table: all 0)
+ * and per pair, on the h x w latent grid (h % hl == 0, w % wl == 0; nearest upsampling):
+ *   mask[j][y][x] = ((bit_j | bit_{n+j})[y / (h / hl)][x / (w / wl)] && (limit == NULL || limit[y][x] != 0)) ? 255 : 0
+ *   area[j] = the number of set cells (area may be NULL)
+ * limit u8 [h * w] or NULL, shared by the pairs.  acc must be finite (a NaN is dropped by the maxima, not propagated).  One workgroup per pair, the two word-sum maps staged in the LDS, no atomics and no
+ * read-back: a relaunch is bit-identical, and every step is reproducible in float32 on the host (tests/blend_ref.py).
+ * 2 <= T <= 128, hl * wl <= 2048, 1 <= n_pos <= 16, h * w <= 2^24.  NULL acc / words / mask, n <= 0, a grid that hl / wl do not divide, th not
+ * finite or a size outside these limits: -22, nothing launched. */
+int tb_blend_mask(const float* acc, const int32_t* words, int n, int T, int hl, int wl, int h, int w, int n_pos, float th,
+                  const uint8_t* limit, uint8_t* mask, int32_t* area, tb_stream_t stream);
+/* tb_dpm_step (same arithmetic through csrc/dpm_step.h, same bits in x, m_prev and x2 of a kept element) for all B = 2n rows, then the
+ * edited rows b >= B / 2 take the source row's NEW value where the pair's mask is zero:
+ *   x[b, j] = mask[b - B / 2][j % hw] ? x[b, j] : x[b - B / 2, j]
+ * mask u8 [B / 2, hw] (non-zero = keep the edit; shared by the channels).  m_prev = every row's own unblended data prediction; x2 = 16-bit
+ * (x | x): tb_dpm_step's conversion of the row's own step where it is kept, and the SOURCE row's x2 bits where it is blended -- an all-zero
+ * mask makes the edited rows equal the source rows in x and x2 bit for bit, an all-255 mask is tb_dpm_step.  (tb_dpm_step_blend, above, is
+ * the inpainting step against a photo; this one blends against the live source row.)  NULL x / eps2 / m_prev / x2 / mask, n_per_b <= 0,
+ * B <= 0, B odd or B > 65535, alpha_t == 0, hw <= 0 or n_per_b % hw != 0: TB_EINVAL, nothing launched. */
+int tb_dpm_step_local_blend(float* x, const void* eps2, float* m_prev, void* x2, int64_t n_per_b, int B, float guidance, float alpha_t,
+                            float sigma_t, float ca, float cb, float cc, const uint8_t* mask, int hw, tb_stream_t stream);
+
 /* ---- CLIP ViT patch embedding (csrc/clip_vision.hip; the image tower of the CLIP-T / CLIP-I evaluation, textboost_amd/clip_score.py) -------
  * img: B resident RGBX images of S x S pixels, image b at img + b * img_stride, rows row_stride pixels apart.  P = (S / patch)^2 patches.
  * w: TB_F16 [D][ldw], K = 4 patch^2 columns in the order (ky, kx, R G B X) then zeros up to Kp (a multiple of 32): the conv weight with

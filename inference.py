@@ -9,6 +9,7 @@ textboost_amd/generate.py.
         [--edit-prompt TEXT] [--reweight WORD=F ...] [--cross-steps F] [--self-steps F]
         [--invert-image photo.jpg [--invert-guidance G] [--mask mask.png [--no-paste]]]
         [--excite WORD [WORD ...] [--excite-steps F] [--excite-scale S] [--excite-loss-scale V] [--no-excite-refine]]
+        [--blend WORD [WORD ...] [--blend-start F] [--blend-threshold T]]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -80,6 +81,16 @@ loss is below 0.05 / 0.5 / 0.8 (--no-excite-refine: one nudge per step).  The 16
 per guided step and seed, the loss before (and, at the refinement steps, after) the nudges, the worst word, the number of nudges and the
 updates skipped because the gradient was not finite.  Works with --with (its main use); not with --region, --edit-prompt, --reweight,
 --invert-image, --init-image, --mask or --attn-map.  The defaults are the paper's; they have not been measured on pretrained weights here.
+
+--blend WORD [WORD ...] keeps an edit where it belongs (textboost_amd/local_blend.py; Prompt-to-Prompt's LocalBlend): with
+--edit-prompt / --reweight, `--prompt "a photo of a dog on a beach" --edit-prompt "a photo of a <dog> dog on a beach" --blend dog "<dog>"`
+swaps the subject and leaves the beach alone.  Every step adds the 16 x 16 cross-attention maps (level 2, as --excite) of both prompts' rows to
+an accumulator; after every solver step from floor(--blend-start F * steps) on (default 0.2) the edited image's latents are set back to the
+source image's, except where the 3 x 3 max-pooled map of the words exceeds --blend-threshold T (default 0.3) times its maximum, in either
+prompt.  Every word is looked up in both prompts and must occur in at least one.  With --invert-image the source row is the photo, and a
+--mask FILE limits the blend mask further.  `<output stem>_blend.png` shows the final masks (one tile per seed, white = edited) and
+`<output stem>_blend.json` the words' token positions in each prompt and the masks' areas; an empty final mask is a printed warning.  Works
+with --with.  The defaults are the published ones; they have not been measured on pretrained weights here.
 
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
@@ -153,7 +164,86 @@ def build_parser():
                    help="with --excite: the factor the 16-bit backward carries the loss with, > 0 (default 256)")
     p.add_argument("--no-excite-refine", dest="no_excite_refine", action="store_true",
                    help="with --excite: no iterative refinement at the steps 0, floor(0.2 steps), floor(0.4 steps)")
+    p.add_argument("--blend", dest="blend", type=str, nargs="+", default=None, metavar="WORD",
+                   help="with --edit-prompt / --reweight (LocalBlend): the edited image keeps the source image's latents except where these words "
+                        "attend (each word must occur in at least one of the two prompts)")
+    p.add_argument("--blend-start", dest="blend_start", type=float, default=None, metavar="F",
+                   help="with --blend: blend behind every step from floor(F * steps) on, 0 <= F <= 1 (default 0.2: the published value, not "
+                        "measured on pretrained weights here)")
+    p.add_argument("--blend-threshold", dest="blend_threshold", type=float, default=None, metavar="T",
+                   help="with --blend: a cell is edited where the pooled attention exceeds T times its maximum, finite and >= 0 (default 0.3: "
+                        "the published value, not measured on pretrained weights here)")
     return p
+
+
+def check_blend_flags(args):
+    """--blend and its companions: the refusals that need no file, by flag name.  -> is the edit blended?"""
+    from textboost_amd import local_blend as B
+    if not args.blend:
+        for flag, given in (("--blend-start", args.blend_start is not None), ("--blend-threshold", args.blend_threshold is not None)):
+            if given:
+                raise SystemExit(f"inference.py: {flag} needs --blend WORD [WORD ...] (the words whose attention bounds the edit)")
+        return False
+    if args.edit_prompt is None and not args.reweight:
+        raise SystemExit("inference.py: --blend needs --edit-prompt TEXT or --reweight WORD=F: it blends the edited image of a prompt-to-prompt "
+                         "pair against its source image")
+    try:
+        if args.blend_start is not None:
+            B.start_step(args.blend_start, args.steps)
+        if args.blend_threshold is not None:
+            B.check_threshold(args.blend_threshold)
+    except B.BlendError as e:
+        raise SystemExit(f"inference.py: {e}")
+    return True
+
+
+def check_blend_args(args, run, p2p, blending):
+    """--blend (`blending`: what `check_blend_flags` returned): the words' token positions in both prompts, on the host, before any model is
+    built.  -> None or {"words", "source", "edit",
+    "found", "start", "threshold"}"""
+    from textboost_amd import local_blend as B
+    if not blending:
+        return None
+    from textboost_amd.attn_maps import run_tokenizer
+    try:
+        tokenizer = run_tokenizer(args.model, run)
+    except OSError as e:
+        raise SystemExit(f"inference.py: --blend: {e} (--model must be a local diffusers model directory)")
+    T = model_text_len(args.model)
+    try:
+        src, edt, found = B.word_positions(tokenizer, args.prompt, p2p["edit_prompt"], args.blend, T)
+        B.position_row(src, T), B.position_row(edt, T)
+    except ValueError as e:      # (BlendError is one)
+        raise SystemExit(f"inference.py: --blend: {e}")
+    return {"words": list(args.blend), "source": src, "edit": edt, "found": found,
+            "start": B.START if args.blend_start is None else args.blend_start,
+            "threshold": B.THRESHOLD if args.blend_threshold is None else args.blend_threshold}
+
+
+def blend_stem(args):
+    return (os.path.splitext(args.output)[0] if args.output is not None else args.prompt.replace(" ", "_")) + "_blend"
+
+
+def write_blend(args, bctl, seeds, cell):
+    """`<stem>_blend.png`: the final masks, nearest x cell, one tile per seed; `<stem>_blend.json`: the positions and the areas (read once)"""
+    import json
+    import numpy as np
+    from PIL import Image
+    stem = blend_stem(args)
+    area = None
+    if bctl.final_mask is None:
+        print(f"--blend: no step was blended (--blend-start {bctl.start:g} of {args.steps} steps): the edit is the plain prompt-to-prompt one")
+    else:
+        masks, area = bctl.final_mask.cpu().numpy(), bctl.area.cpu().tolist()
+        tiles = [np.kron(m, np.ones((cell, cell), dtype=np.uint8)) for m in masks]
+        Image.fromarray(np.concatenate(tiles, axis=1)).save(stem + ".png")
+        for s, a in zip(seeds, area):
+            if a == 0:
+                print(f"warning: --blend: the final mask of seed {s} is empty: the edited image is the source image")
+    with open(stem + ".json", "w") as f:
+        json.dump(dict(bctl.report(area=area, seeds=None), prompt=args.prompt, edit_prompt=args.edit_prompt, seeds=[str(s) for s in seeds]), f,
+                  indent=1, sort_keys=True)
+    print(f"wrote {stem}.json" + (f" and {stem}.png: {area} of {bctl.h * bctl.w} latent cells edited" if area is not None else ""))
 
 
 def check_excite_flags(args):
@@ -265,7 +355,8 @@ def load_runs(args):
                 [("--region", r) for r in (getattr(args, "region", None) or [])] + \
                 [("--edit-prompt", t) for t in [getattr(args, "edit_prompt", None)] if t is not None] + \
                 [("--reweight", r) for r in (getattr(args, "reweight", None) or [])] + \
-                [("--excite", w) for w in (getattr(args, "excite", None) or [])]:
+                [("--excite", w) for w in (getattr(args, "excite", None) or [])] + \
+                [("--blend", w) for w in (getattr(args, "blend", None) or [])]:
             if tok in text:
                 raise SystemExit(f"inference.py: {what} {text!r} uses {tok}, which both {first[tok]} and {dropped} hold: ambiguous (the first "
                                  "run's vector would be taken); rename the token in one run or leave it out of the prompt")
@@ -538,6 +629,7 @@ def main(argv=None):
     check_excite_flags(args)
     check_invert_flags(args)
     check_p2p_flags(args)
+    blending = check_blend_flags(args)
     run = load_runs(args)
     words = positions = None
     if args.attn_map is not None:        # every refusal before anything reaches the device
@@ -547,6 +639,7 @@ def main(argv=None):
     p2p = check_p2p_args(args, run)
     invert = check_invert_args(args)
     excite = check_excite_args(args, run)
+    blend = check_blend_args(args, run, p2p, blending)
     seeds = args.seeds
     if invert is not None:
         seeds = ["inv"]        # one photo, one deterministic edit: the file names carry `inv` in the seed's place
@@ -596,6 +689,12 @@ def main(argv=None):
             from textboost_amd.p2p import P2PControl
             ctl = P2PControl.for_unet(pipe.unet, p2p["plan"], cross_steps=p2p["cross"], self_steps=p2p["self"])
             what += f", edit prompt {p2p['edit_prompt']!r}"
+        bctl = None
+        if blend is not None:
+            from textboost_amd.local_blend import BlendControl
+            bctl = BlendControl(pipe.unet, blend["source"], blend["edit"], words=blend["words"], start=blend["start"],
+                                threshold=blend["threshold"], found=blend["found"])
+            what += f", blend {blend['words']}"
         if invert is not None:      # the photo is encoded once and inverted under --prompt; the source row is pinned to that trajectory
             import numpy as np
             from textboost_amd import edit as E
@@ -610,7 +709,8 @@ def main(argv=None):
                 if not args.no_paste:
                     pixel_mask = torch.from_numpy(np.ascontiguousarray(pm)).to(pipe.dev)
             rgbx = pipe.invert_edit_images(states[1], states[0], z0, ctl, invert_guidance=invert["guidance"], latent_mask=latent_mask,
-                                           pixel_mask=pixel_mask, init_rgbx=init_rgbx if pixel_mask is not None else None, what=what)
+                                           pixel_mask=pixel_mask, init_rgbx=init_rgbx if pixel_mask is not None else None, what=what,
+                                           blend=bctl)
         elif excite is not None:      # Attend-and-Excite (textboost_amd/excite.py): every refusal has happened on the host already
             import json
             from textboost_amd.excite import ExciteControl
@@ -621,7 +721,7 @@ def main(argv=None):
                 json.dump(dict(xctl.report(), prompt=args.prompt, seeds=list(seeds)), f, indent=1)
             print(f"wrote {excite_path(args)}: {len(xctl.trace)} guided step(s), {xctl.skipped} skipped update(s)")
         elif edit is None:
-            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps, p2p=ctl)
+            rgbx = pipe.images(states[1], states[0], latents, what=what, maps=recorder, regions=rset, region_steps=rsteps, p2p=ctl, blend=bctl)
         else:       # a seed's latent is the noise of its image; the photo is encoded once
             import numpy as np
             from textboost_amd import edit as E
@@ -642,6 +742,8 @@ def main(argv=None):
                                     region_steps=rsteps)
         from PIL import Image
         images = [Image.fromarray(augment.to_host_rgb(rgbx[k])) for k in range(n)]
+        if bctl is not None:
+            write_blend(args, bctl, seeds, images[0].width // pipe.size)
         word_maps = None
         if recorder is not None:
             from textboost_amd.attn_maps import word_map

@@ -408,13 +408,17 @@ class Pipeline:
         """the UNet of one trained run: its K/V adapters folded in, or the base weights"""
         self.set_unet_adapters([(run.unet_lora, run.unet_rank, 1.0)] if run.unet_rank else [])
 
-    def images(self, cond, uncond, latents, what: str = "", maps=None, regions=None, region_steps=None, p2p=None, excite=None) -> torch.Tensor:
+    def images(self, cond, uncond, latents, what: str = "", maps=None, regions=None, region_steps=None, p2p=None, excite=None,
+               blend=None) -> torch.Tensor:
         """text states fp32 [B*T, D] twice, latents fp32 [B, 4, size, size] on the device -> int32 RGBX [B, 8 size, 8 size] (resident).
         Non-finite final latents raise before anything is decoded.  maps: an `attn_maps.AttnMapRecorder` of `self.unet` (the images do not
         change with it).  regions / region_steps: a `regions.RegionSet` of `self.unet` and how many steps it acts on (`HipSampler.denoise`).
         p2p: a `p2p.P2PControl` of `self.unet`: rows [0, B/2) are the source images, [B/2, B) the edited ones.
-        excite: an `excite.ExciteControl` of `self.unet` (Attend-and-Excite; its trace is filled by the call)."""
-        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps, regions=regions, region_steps=region_steps, p2p=p2p, excite=excite)
+        excite: an `excite.ExciteControl` of `self.unet` (Attend-and-Excite; its trace is filled by the call).
+        blend: a `local_blend.BlendControl` of `self.unet` (with `p2p`): the edited rows keep the source rows' latents outside the words'
+        attention; its `final_mask` / `area` are left on the device."""
+        x = self.sampler.denoise(cond, uncond, latents=latents, maps=maps, regions=regions, region_steps=region_steps, p2p=p2p, excite=excite,
+                                 blend=blend)
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         return self.vae.decode_rgbx(x)
@@ -440,21 +444,22 @@ class Pipeline:
         return out
 
     def invert_edit_images(self, cond, uncond, z0, p2p, invert_guidance: float = 1.0, latent_mask=None, pixel_mask=None, init_rgbx=None,
-                           what: str = "") -> torch.Tensor:
+                           what: str = "", blend=None) -> torch.Tensor:
         """A photo edited by its prompt: rows [0, B/2) carry the prompt that describes the photo, rows [B/2, B) the edit
         prompt.  z0 fp32 [1, 4, size, size] (the encoded photo) is inverted under row 0's prompt (`HipSampler.invert`, guidance
         `invert_guidance`), then the prompt-to-prompt denoise runs with the source rows pinned to that trajectory (`denoise(p2p=, pin=)`):
         they end as z0 exactly, so their image is the VAE round trip of the photo.  latent_mask uint8 [size, size] or None (non-zero =
         repaint): the edited rows' other cells stay on the trajectory too.  With pixel_mask (uint8 [8 size, 8 size]) and init_rgbx (the
         prepared photo, int32 RGBX) the photo's bytes are pasted outside the mask into the EDITED rows only; the source rows stay the plain
-        decode.  -> int32 RGBX [B, 8 size, 8 size] (resident)."""
+        decode.  blend: a `local_blend.BlendControl` (one pair): from its start step on the edited row leaves the trajectory only where the
+        words attend (inside latent_mask, when given).  -> int32 RGBX [B, 8 size, 8 size] (resident)."""
         from . import ops
         if (pixel_mask is None) != (init_rgbx is None):
             raise ValueError("the paste needs both pixel_mask and init_rgbx")
         if p2p is None:
             raise ValueError("invert_edit_images needs the prompt-to-prompt control of the edit")
         traj = self.sampler.invert(cond, uncond, z0, guidance=invert_guidance)
-        x = self.sampler.denoise(cond, uncond, p2p=p2p, pin=traj[:, 0], pin_mask=latent_mask)
+        x = self.sampler.denoise(cond, uncond, p2p=p2p, pin=traj[:, 0], pin_mask=latent_mask, blend=blend)
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} inversion and {self.steps} denoising steps: {what}")
         rgbx = self.vae.decode_rgbx(x)

@@ -596,6 +596,35 @@ def dpm_step_pin(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sigma_t, ca
             L.ptr(pin), n_src, L.ptr(mask), hw)
 
 
+def blend_mask(acc, words, h, w, hl, wl, th, mask, limit=None, area=None):
+    """The LocalBlend masks of n prompt-to-prompt pairs (csrc/local_blend.hip): acc fp32 [2n, T, hl * wl] (the
+    accumulator of `attn_token_maps` for the rows c_src | c_edit), words int32 [2n, n_pos] (-1 padded) -> mask uint8 [n, h * w] (255 where
+    the 3 x 3 max of a row's word-sum map exceeds th times its maximum, in the source or the edited row; nearest upsampling), ANDed with
+    limit uint8 [h * w] != 0 when given; area int32 [n] (optional) = the set cells of every mask."""
+    n2, T, HW = acc.shape
+    n = n2 // 2
+    assert n2 == 2 * n and HW == hl * wl and acc.dtype == torch.float32 and acc.is_contiguous()
+    assert words.dim() == 2 and words.shape[0] == n2 and words.dtype == torch.int32 and words.is_contiguous()
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == n * h * w
+    assert limit is None or (limit.dtype == torch.uint8 and limit.is_contiguous() and limit.numel() == h * w)
+    assert area is None or (area.dtype == torch.int32 and area.is_contiguous() and area.numel() == n)
+    _launch("tb_blend_mask", L.ptr(acc), L.ptr(words), n, T, hl, wl, h, w, words.shape[1], th, L.ptr(limit), L.ptr(mask), L.ptr(area))
+    return mask
+
+
+def dpm_step_local_blend(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sigma_t, ca, cb, cc, mask, hw):
+    """`dpm_step` for all B = 2n rows, then the edited rows [n, 2n) take the source rows' new value where their pair's mask is zero, in the
+    same launch (csrc/local_blend.hip).  mask uint8 [n, hw] (non-zero = keep the edit; shared by the channels).  (`dpm_step_blend` is the
+    inpainting step against a photo's latents; this one blends against the live source row.)"""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (x, m_prev)) and B % 2 == 0
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == (B // 2) * hw
+    assert eps2.dtype == L.half_dtype() and x2.dtype == L.half_dtype() and eps2.is_contiguous() and x2.is_contiguous()
+    assert x.numel() == B * n_per_b and m_prev.numel() == B * n_per_b
+    assert eps2.numel() == 2 * B * n_per_b and x2.numel() == 2 * B * n_per_b
+    _launch("tb_dpm_step_local_blend", L.ptr(x), L.ptr(eps2), L.ptr(m_prev), L.ptr(x2), n_per_b, B, guidance, alpha_t, sigma_t, ca, cb, cc,
+            L.ptr(mask), hw)
+
+
 def img_paste(gen, orig, mask, out=None):
     """mask ? gen : orig per pixel: gen / orig int32 RGBX [H, W] (rows may be strided), mask uint8 [H, W] (non-zero = gen) -> int32 [H, W]"""
     h, w = gen.shape

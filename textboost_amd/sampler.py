@@ -201,7 +201,7 @@ class HipSampler:
         self.generator: Optional[torch.Generator] = None
 
     def denoise(self, cond_ehs, uncond_ehs, latents=None, step_noise=None, maps=None, regions=None, region_steps=None, p2p=None, pin=None,
-                pin_mask=None, excite=None):
+                pin_mask=None, excite=None, blend=None):
         """cond / uncond: fp16 or fp32 [B*77, D] text-encoder outputs.  Returns the final latents fp32 [B,4,h,w].
         step_noise (ancestral schedulers only): one [B,4,h,w] tensor per step instead of drawing from `self.generator`.
         maps: an `attn_maps.AttnMapRecorder` of this UNet (rows [B, 2B): the conditional half); it is zeroed here and records every step.
@@ -222,8 +222,17 @@ class HipSampler:
         times, until every image's loss is below {0.05, 0.5, 0.8}: the one place where the host reads the [B] losses; an image already
         below gets step 0.  A non-finite gradient skips that image's update and is counted in `excite.skipped`, never raised.
         `excite.trace` holds one entry per guided step.  Not with `maps`, `regions`, `p2p` or `pin`: ValueError.  Without `excite` the method
-        launches what it launched before."""
+        launches what it launched before.
+        blend: a `local_blend.BlendControl` of this UNet (prompt-to-prompt LocalBlend; needs `p2p`).  Every step's forward adds
+        the conditional rows' level-2 cross-attention maps to an accumulator (zeroed here).  Steps i < floor(blend.start * steps) run the step
+        launch they run without it; from there on a step is `tb_blend_mask` (the accumulator, step i's forward included -> one mask per pair)
+        and ONE `tb_dpm_step_local_blend`: x_edit = mask ? x_edit : x_src, x_src the source row after the same step.  With `pin` (one pair):
+        `tb_blend_mask(limit = pin_mask)`, then the usual `tb_dpm_step_pin` with that mask in `pin_mask`'s place.  No host synchronisation.
+        `blend.final_mask` / `blend.area` are the last step's masks on the device (None when no step blended); `blend.keep_masks` keeps every
+        step's in `blend.masks`.  Not without `p2p`, not with `maps`, `regions` or `excite`: ValueError.  `unet.blend` is set during the call
+        only; without `blend` the method launches what it launched before."""
         B, sch = self.B, self.sch
+        bl_start = self._blend_start(blend, p2p, maps, regions, excite, pin)
         ex_steps = self._excite_steps(excite, maps, regions, p2p, pin)
         p2p_cross, p2p_self = self._p2p_steps(p2p, maps, regions)
         region_steps = self._region_steps(regions, region_steps, self.steps)
@@ -232,6 +241,13 @@ class HipSampler:
             p2p.reset()
         if maps is not None:
             maps.zero()
+        bl = None
+        if blend is not None:
+            bl = self._blend_bufs
+            bl.words.copy_(blend.table)
+            bl.acc.zero_()
+            blend.final_mask = blend.area = None
+            blend.masks = torch.zeros((self.steps,) + tuple(bl.mask.shape), dtype=torch.uint8, device=self.x.device) if blend.keep_masks else None
         if pin is not None:
             self.x.copy_(pin[0].expand_as(self.x))
         else:
@@ -247,11 +263,28 @@ class HipSampler:
         for i in range(self.steps):
             if i < ex_steps:
                 self._excite_pass(i, ehs, excite)
-            eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None, p2p, i < p2p_cross, i < p2p_self)
+            if bl is None:
+                eps2 = self._unet_forward(i, ehs, maps, regions if i < region_steps else None, p2p, i < p2p_cross, i < p2p_self)
+            else:   # the same forward; its level-2 cross-attention layers also record the conditional rows' maps
+                self.unet.blend, bl.record = bl, True
+                try:
+                    eps2 = self._unet_forward(i, ehs, None, None, p2p, i < p2p_cross, i < p2p_self)
+                finally:
+                    self.unet.blend, bl.record = None, False
             a_t, s_t = sch.data_prediction_scalars(i)
             ca, cb, cc = sch.coefficients(i)
+            blending = bl is not None and i >= bl_start
+            if blending:
+                ops.blend_mask(bl.acc, bl.words, self.x.shape[2], self.x.shape[3], bl.h, bl.w, blend.threshold, bl.mask, limit=pin_mask, area=bl.area)
+                if blend.masks is not None:
+                    blend.masks[i].copy_(bl.mask)
+                blend.final_mask, blend.area = bl.mask, bl.area
             if pin is not None:
-                ops.dpm_step_pin(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc, pin[i + 1], B // 2, pin_mask, hw)
+                ops.dpm_step_pin(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc, pin[i + 1], B // 2,
+                                 bl.mask if blending else pin_mask, hw)
+                continue
+            if blending:
+                ops.dpm_step_local_blend(self.x, eps2, self.m_prev, self.x2, n, B, self.g, a_t, s_t, ca, cb, cc, bl.mask, hw)
                 continue
             if getattr(sch, "needs_noise", False):  # the variance noise of the ancestral step rides in the m_prev operand
                 if step_noise is not None:
@@ -262,6 +295,47 @@ class HipSampler:
         if ex_steps:
             self._excite_finish(excite)
         return self.x
+
+    # ------------------------------------------------------------------ prompt-to-prompt LocalBlend (local_blend.py)
+    def _blend_start(self, blend, p2p, maps, regions, excite, pin):
+        """the first step of `denoise` whose launch blends; every refusal, before anything is touched.  Allocates the recorder's buffers on
+        first use (`HipUNet.enable_blend`); they stay with the sampler, and `unet.blend` is set only while `denoise` runs."""
+        if blend is None:
+            return None
+        from .local_blend import start_step
+        if p2p is None:
+            raise ValueError("blend without p2p: LocalBlend blends the edited rows of a prompt-to-prompt pair against their source rows")
+        for name, given in (("maps", maps), ("regions", regions), ("excite", excite)):
+            if given is not None:
+                raise ValueError(f"LocalBlend does not go with {name} (prompt-to-prompt, which it needs, does not either)")
+        unet = self.unet
+        if 2 * blend.n != self.B or blend.T != unet.T or (blend.h, blend.w) != (unet.H, unet.W):
+            raise ValueError(f"the blend control is built for {blend.n} pairs, {blend.T} tokens and a {blend.h} x {blend.w} grid; the sampler "
+                             f"runs {self.B} rows, {unet.T} tokens, {unet.H} x {unet.W}")
+        if pin is not None and self.B != 2:
+            raise ValueError(f"blend with pin takes one pair (the pinned step's mask is shared by the rows), not {self.B // 2}")
+        start = start_step(blend.start, self.steps)
+        bl = getattr(self, "_blend_bufs", None)
+        if bl is None or bl.n_pos != blend.n_pos:
+            prev = unet.blend
+            try:
+                bl = unet.enable_blend(n_pos=blend.n_pos)   # (NotImplementedError for an fp32 UNet, ValueError without level-2 cross-attention)
+            finally:
+                unet.blend = prev
+            self._blend_bufs = bl
+        if tuple(bl.words.shape) != tuple(blend.table.shape):
+            raise ValueError(f"the blend control's table is {tuple(blend.table.shape)}; the sampler needs {tuple(bl.words.shape)}")
+        return start
+
+    @property
+    def blend_buffers(self):
+        """the recorder's buffers of the last `denoise(blend=)` (`HipUNet.enable_blend`'s namespace: acc, words, mask, area, layers, ...);
+        None before the first"""
+        return getattr(self, "_blend_bufs", None)
+
+    def forward_step(self, i, ehs, p2p=None, p2p_cross=False, p2p_self=False):
+        """the UNet call of step i of `denoise` on the sampler's current `x2`, as `denoise` issues it (tests replay a generation with it)"""
+        return self._unet_forward(i, ehs, None, None, p2p, p2p_cross, p2p_self)
 
     # ------------------------------------------------------------------ Attend-and-Excite (excite.py, DESIGN.md 22)
     def _excite_steps(self, excite, maps, regions, p2p, pin):

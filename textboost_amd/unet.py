@@ -122,6 +122,8 @@ class HipUNet:
         self.p2p = None         # a p2p.P2PControl: extra launches overwrite the edited conditional rows of the attention outputs (opt-in; None = the plain forward, launch for launch)
         self.attn_loss = None   # enable_attn_loss(): the cross-attention localisation loss in the backward of the supervised layers (None = no launch)
         self.excite = None      # enable_excite(): Attend-and-Excite -- forward(until="excite") / backward_sample() record and inject (None = no launch)
+        self.blend = None       # enable_blend(): prompt-to-prompt LocalBlend -- a full forward records the conditional rows' level-2 maps (None = no launch)
+        self._cut = None        # the layer a truncated forward (until="excite") stops behind; None in a normal forward
         self._bwd_through = False   # backward_sample(): the backward does not stop at the first cross-attention
         self._bufs: Dict[str, torch.Tensor] = {}
         self.tape: List = []
@@ -216,6 +218,37 @@ class HipUNet:
         ex = self.excite
         ops.excite_loss(ex.acc, ex.last, ex.words, ex.h, ex.w, loss_scale, ex.loss, ex.word, ex.sel, ex.dA, check=check)
         return ex.loss
+
+    # ------------------------------------------------------------------ prompt-to-prompt LocalBlend
+    BLEND_LEVEL = 2   # the recorded maps: (H >> 2) x (W >> 2), as Attend-and-Excite's
+
+    def enable_blend(self, n_pos: int = 16):
+        """--blend: with `blend.record` set, the level-2 cross-attention layers of a normal (untruncated) forward add the head-and-layer mean
+        of their probabilities for the 2n conditional rows c_src | c_edit of a prompt-to-prompt batch (UNet rows [2n, 4n)) to `blend.acc`
+        fp32 [2n, T, h_l * w_l] -- each row's own uncontrolled softmax (`ops.attn_token_maps`), behind the prompt-to-prompt launch.  The
+        caller zeroes `blend.acc` and writes `blend.words` int32 [2n, n_pos] (-1 until then).  Every buffer is allocated here."""
+        if self.dtype == torch.float32:
+            raise NotImplementedError("LocalBlend has 16-bit kernels only (an fp32 UNet records no attention maps)")
+        if self.B % 4:
+            raise ValueError(f"LocalBlend takes a guidance UNet of batch 4n (source and edited rows, unconditional and conditional), not {self.B}")
+        lvl = self.BLEND_LEVEL
+        layers = [p for p, _ in self.xattn if self.xattn_level[p] == lvl]
+        if not layers:
+            raise ValueError(f"LocalBlend reads the cross-attention maps of level {lvl}; this UNet has cross-attention on levels "
+                             f"{sorted(set(self.xattn_level.values()))} only")
+        if not 2 <= self.T <= 128:
+            raise ValueError(f"LocalBlend takes 2 .. 128 prompt tokens; the UNet is built for {self.T}")
+        h, w = self.H >> lvl, self.W >> lvl
+        if h < 1 or w < 1 or h * w > 2048 or self.H % h or self.W % w:
+            raise ValueError(f"the level-{lvl} map of a {self.H} x {self.W} grid is {h} x {w}: LocalBlend needs 1 .. 2048 positions that divide the grid")
+        n2, dev = self.B // 2, self.dev
+        bl = SimpleNamespace(level=lvl, layers=set(layers), n=len(layers), b0=n2, nb=n2, h=h, w=w, n_pos=int(n_pos), record=False)
+        bl.acc = torch.zeros(n2, self.T, h * w, device=dev)
+        bl.words = torch.full((n2, int(n_pos)), -1, dtype=torch.int32, device=dev)
+        bl.mask = torch.zeros(n2 // 2, self.H, self.W, dtype=torch.uint8, device=dev)
+        bl.area = torch.zeros(n2 // 2, dtype=torch.int32, device=dev)
+        self.blend = bl
+        return bl
 
     # ------------------------------------------------------------------ cross-attention K/V adapters (SURVEY 8(f).4)
     def enable_kv_lora(self, r: int, alpha: Optional[float] = None, seed: Optional[int] = None):
@@ -593,6 +626,9 @@ class HipUNet:
         ex = self.excite
         if ex is not None and ex.record and (tb + ".attn2") in ex.layers:   # Attend-and-Excite: the mean over the supervised layers and heads
             ops.attn_token_maps(q2, k2, ex.acc, B, heads, HW, T, hd, b0=ex.b0, nb=ex.nb, w=1.0 / (heads * ex.n), accumulate=True)
+        bl = self.blend
+        if bl is not None and bl.record and self._cut is None and (tb + ".attn2") in bl.layers:   # LocalBlend: the conditional rows' own maps
+            ops.attn_token_maps(q2, k2, bl.acc, B, heads, HW, T, hd, b0=bl.b0, nb=bl.nb, w=1.0 / (heads * bl.n), accumulate=True)
         t2 = self.buf(prefix + ".t2", M, C)
         # --- GEGLU feed-forward
         ls3 = self.buf(prefix + ".ls3", M, 2, torch.float32)
@@ -736,6 +772,7 @@ class HipUNet:
         return self._forward(sample, timesteps, ehs16, ehs_ready)
 
     def _forward(self, sample, timesteps, ehs16, ehs_ready=None, cut=None):
+        self._cut = cut
         if self.excite is not None and self.excite.record:
             self.excite.acc.zero_()
         geo, B, P = self.geo, self.B, self.P
