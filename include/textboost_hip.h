@@ -726,6 +726,43 @@ int tb_blend_mask(const float* acc, const int32_t* words, int n, int T, int hl, 
 int tb_dpm_step_local_blend(float* x, const void* eps2, float* m_prev, void* x2, int64_t n_per_b, int B, float guidance, float alpha_t,
                             float sigma_t, float ca, float cb, float cc, const uint8_t* mask, int hw, tb_stream_t stream);
 
+/* ---- MultiDiffusion canvas (csrc/canvas.hip; inference.py --width / --height, textboost_amd/canvas.py, HipSampler.denoise_canvas,
+ * Pipeline.canvas_images) ----
+ * A canvas x fp32 [n, 4, Hc, Wc] is denoised as overlapping S x S windows.  Per axis the window origins are a table: oy[ny], ox[nx], int32,
+ * strictly increasing, first 0, last L - S, no gap (o[k+1] - o[k] <= S).  Window k = iy * nx + ix, pair p = img * ny * nx + k, pairs cut
+ * into chunks of Bu.  Every table is passed twice: `*_host` is read and checked by the entry point (a table that breaks the rules above:
+ * TB_EINVAL), `*_dev` holds the same values on the device and is what the kernel reads, each origin clamped to [0, L - S] there, so no
+ * content of the device copy addresses outside the canvas.
+ *
+ * tb_canvas_gather: x2 (16-bit [2 Bu, 4, S, S]) rows r and Bu + r = the crop of pair min(chunk * Bu + r, n * ny * nx - 1): rows past the end
+ * of the pair list repeat the last valid pair.  The crop is (f16)x, or a copy of xh when xh (16-bit [n, 4, Hc, Wc], tb_canvas_step's) is
+ * given.  NULL x / x2 / tables, a non-positive size, Hc or Wc < S, Bu > 65535, chunk outside 0 .. ceil(pairs / Bu) - 1: TB_EINVAL, nothing
+ * launched. */
+int tb_canvas_gather(const float* x, const void* xh, void* x2, int n, int Hc, int Wc, int S, const int32_t* oy_dev, const int32_t* oy_host,
+                     int ny, const int32_t* ox_dev, const int32_t* ox_host, int nx, int Bu, int chunk, tb_stream_t stream);
+/* tb_canvas_step: one guided DPM-Solver++(2M) step of the whole canvas.  eps_all 16-bit [n_chunks, 2 Bu, 4, S, S]: every chunk's UNet
+ * output (uncond | cond), chunk = p / Bu, row = p % Bu.  Per canvas element, over the covering windows in ascending k:
+ *   eps = (sum_k e_u + g (e_c - e_u)) / count      (fp32)      then tb_dpm_step's update through csrc/dpm_step.h:
+ *   m0 = (x - sigma_t eps) / alpha_t ;  x = ca x + cb m0 + cc m_prev ;  m_prev = m0
+ * One thread owns one element and reads only rows of valid pairs; no atomics: a relaunch on the same operands is bit-identical.  With one
+ * window (Hc == Wc == S) x and m_prev carry tb_dpm_step's bits.  xh (may be NULL): 16-bit [n, 4, Hc, Wc] = tb_dpm_step's conversion of the
+ * new x (in the fp16 build one rounding of the update's last fma, which differs from (f16)x on ties), so that the next gather feeds the UNet
+ * tb_dpm_step's x2 bits.  NULL x / eps_all / m_prev / tables, a non-positive size, Hc or Wc < S, Bu > 65535, alpha_t == 0: TB_EINVAL,
+ * nothing launched. */
+int tb_canvas_step(float* x, const void* eps_all, float* m_prev, void* xh, int n, int Hc, int Wc, int S, const int32_t* oy_dev,
+                   const int32_t* oy_host, int ny, const int32_t* ox_dev, const int32_t* ox_host, int nx, int Bu, float guidance,
+                   float alpha_t, float sigma_t, float ca, float cb, float cc, tb_stream_t stream);
+/* tb_tile_blend: decoded VAE tiles -> one image.  tiles fp32 NHWC rows [n * nty * ntx * P * P, ld >= 3] (R, G, B first; what the decoder
+ * leaves in front of tb_vae_image), tile t = img * nty * ntx + iy * ntx + ix of P x P pixels at origin (ty[iy], tx[ix]) of the Hp x Wp
+ * image (tables as above, in pixels, with P for S).  Per axis, a tile at origin O on an axis of Lp pixels, ramp R >= 1, pixel t:
+ *   lo = (O == 0) ? R : min(t - O + 1, R) ;  hi = (O + P == Lp) ? R : min(O + P - t, R) ;  w_axis = min(lo, hi) / R ;  w = w_y w_x
+ *   value = sum w v / sum w   (fp32, covering tiles in ascending order)
+ * image (may be NULL) fp32 NCHW [n, 3, Hp, Wp] = clamp(value / 2 + 0.5, 0, 1), tb_vae_image's rule; rgbx (may be NULL) u32 [n, Hp, Wp] =
+ * tb_vae_image_rgbx's bytes of value.  A single tile has w = 1 and gives those two kernels' bits.  NULL tiles / tables or both outputs
+ * NULL, a non-positive size, ld < 3, Hp or Wp < P, ramp < 1: TB_EINVAL, nothing launched. */
+int tb_tile_blend(const float* tiles, int64_t ld, float* image, uint32_t* rgbx, int n, int Hp, int Wp, int P, const int32_t* ty_dev,
+                  const int32_t* ty_host, int nty, const int32_t* tx_dev, const int32_t* tx_host, int ntx, int ramp, tb_stream_t stream);
+
 /* ---- CLIP ViT patch embedding (csrc/clip_vision.hip; the image tower of the CLIP-T / CLIP-I evaluation, textboost_amd/clip_score.py) -------
  * img: B resident RGBX images of S x S pixels, image b at img + b * img_stride, rows row_stride pixels apart.  P = (S / patch)^2 patches.
  * w: TB_F16 [D][ldw], K = 4 patch^2 columns in the order (ky, kx, R G B X) then zeros up to Kp (a multiple of 32): the conv weight with

@@ -10,6 +10,7 @@ textboost_amd/generate.py.
         [--invert-image photo.jpg [--invert-guidance G] [--mask mask.png [--no-paste]]]
         [--excite WORD [WORD ...] [--excite-steps F] [--excite-scale S] [--excite-loss-scale V] [--no-excite-refine]]
         [--blend WORD [WORD ...] [--blend-start F] [--blend-threshold T]]
+        [--width PX] [--height PX] [--window-stride CELLS]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -92,6 +93,16 @@ prompt.  Every word is looked up in both prompts and must occur in at least one.
 `<output stem>_blend.json` the words' token positions in each prompt and the masks' areas; an empty final mask is a printed warning.  Works
 with --with.  The defaults are the published ones; they have not been measured on pretrained weights here.
 
+--width PX / --height PX make a banner, a panorama or a portrait-format picture (textboost_amd/canvas.py; MultiDiffusion, Bar-Tal
+et al. 2023): `--width 2048` on an SD1.x model writes 2048 x 512 images.  The UNet is not run at that shape: the large latent is denoised as
+overlapping windows of the model's own size, --window-stride CELLS latent cells apart (default a quarter of the model's latent side: 13 windows
+for 2048 pixels at SD1.x), whose noise predictions are averaged where they overlap before the ONE solver step of the whole canvas; the result is
+decoded as VAE tiles that are feathered where they overlap.  Either flag alone leaves the other side at the model's size; sides are multiples
+of the VAE's factor, at least the model's size and at most 8192 pixels.  All windows share --prompt.  --with, --weights and --checkpoint work as
+before.  Not with --init-image, --mask, --invert-image, --edit-prompt, --reweight, --region, --excite, --attn-map or --blend: each of them
+places things on the model's own grid.  The paper's stride is 8 cells; the default here is a cost choice and has not been measured on pretrained
+weights.
+
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
 latent of a seed is drawn on the CPU (textboost_amd.generate.seeded_latent), the same on every machine."""
@@ -173,7 +184,64 @@ def build_parser():
     p.add_argument("--blend-threshold", dest="blend_threshold", type=float, default=None, metavar="T",
                    help="with --blend: a cell is edited where the pooled attention exceeds T times its maximum, finite and >= 0 (default 0.3: "
                         "the published value, not measured on pretrained weights here)")
+    p.add_argument("--width", type=int, default=None, metavar="PX",
+                   help="image width in pixels: a multiple of the VAE's factor, from the model's size to 8192 (a wider picture is denoised as "
+                        "overlapping windows of the model's size: MultiDiffusion)")
+    p.add_argument("--height", type=int, default=None, metavar="PX", help="image height in pixels, as --width")
+    p.add_argument("--window-stride", dest="window_stride", type=int, default=None, metavar="CELLS",
+                   help="with --width / --height: latent cells between neighbouring windows, 1 .. the model's latent side (default a quarter "
+                        "of it, 16 at SD1.x, where the paper uses 8: a cost choice, not measured on pretrained weights here)")
     return p
+
+
+MAX_CANVAS_PX = 8192
+CANVAS_UNET_BATCH = 13      # image-window pairs per UNet call: the generation batch the kernels are tuned for
+
+
+def check_canvas_flags(args):
+    """--width / --height / --window-stride: every refusal, on the host, before any model is built.  -> None (the model's own square) or
+    {"Hc", "Wc": the canvas in latent cells, "stride", "S": the model's latent side, "factor": the VAE's}"""
+    import json
+    from textboost_amd.canvas import CanvasError, CanvasPlan
+    if args.width is None and args.height is None:
+        if args.window_stride is not None:
+            raise SystemExit("inference.py: --window-stride needs --width PX or --height PX (the canvas whose windows it spaces)")
+        return None
+    why = {"--init-image": "a photo is prepared and encoded at the model's own size; a canvas-sized photo is not built",
+           "--mask": "a mask belongs to --init-image / --invert-image, which the canvas does not go with",
+           "--invert-image": "the inversion walks one model-sized latent up the schedule, not a canvas of windows",
+           "--edit-prompt": "the prompt-to-prompt control pairs the rows of one UNet batch, and a canvas's windows fill that batch",
+           "--reweight": "the prompt-to-prompt control pairs the rows of one UNet batch, and a canvas's windows fill that batch",
+           "--region": "a region is a part of the model's own grid; mapping it onto every window of a canvas is not built",
+           "--excite": "the excite pass moves the latents of one model-sized image; the windows of a canvas overlap and would be moved apart",
+           "--attn-map": "the recorder accumulates maps of the model's own grid; stitching the windows' maps is not built",
+           "--blend": "LocalBlend needs --edit-prompt / --reweight, which the canvas does not go with"}
+    for flag, given in (("--init-image", args.init_image is not None), ("--mask", args.mask is not None),
+                        ("--invert-image", args.invert_image is not None), ("--edit-prompt", args.edit_prompt is not None),
+                        ("--reweight", bool(args.reweight)), ("--region", bool(args.region)), ("--excite", bool(args.excite)),
+                        ("--attn-map", args.attn_map is not None), ("--blend", bool(args.blend))):
+        if given:
+            raise SystemExit(f"inference.py: --width / --height do not go with {flag}: {why[flag]}")
+    try:
+        with open(os.path.join(args.model, "unet", "config.json")) as f:
+            S = int(json.load(f).get("sample_size", 64))
+        with open(os.path.join(args.model, "vae", "config.json")) as f:
+            factor = 1 << (len(json.load(f).get("block_out_channels", [0] * 4)) - 1)
+    except OSError as e:
+        raise SystemExit(f"inference.py: --width / --height: {e} (--model must be a local diffusers model directory)")
+    cells = {}
+    for flag, px in (("--width", args.width), ("--height", args.height)):
+        px = S * factor if px is None else px
+        if px % factor or not S * factor <= px <= MAX_CANVAS_PX:
+            raise SystemExit(f"inference.py: {flag} {px}: a multiple of {factor} (the VAE's factor) from {S * factor} (the model's size) to "
+                             f"{MAX_CANVAS_PX} pixels")
+        cells[flag] = px // factor
+    stride = max(1, S // 4) if args.window_stride is None else args.window_stride
+    try:
+        CanvasPlan(S, cells["--height"], cells["--width"], stride, len(args.seeds), CANVAS_UNET_BATCH)
+    except CanvasError as e:
+        raise SystemExit(f"inference.py: --window-stride: {e}")
+    return {"Hc": cells["--height"], "Wc": cells["--width"], "stride": stride, "S": S, "factor": factor}
 
 
 def check_blend_flags(args):
@@ -626,6 +694,7 @@ def main(argv=None):
     if not args.model:
         raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
     G.check_model_dir(args.model, "inference.py")
+    canvas = check_canvas_flags(args)
     check_excite_flags(args)
     check_invert_flags(args)
     check_p2p_flags(args)
@@ -650,10 +719,14 @@ def main(argv=None):
     from textboost_amd import augment
     nseeds = len(seeds)
     n = 2 * nseeds if p2p is not None else nseeds      # prompt-to-prompt: the source rows, then the edited rows
+    nb = n      # rows of the executors' batch: the images, or (canvas) the image-window pairs of one UNet call
+    if canvas is not None:
+        from textboost_amd.canvas import CanvasPlan
+        nb = min(CanvasPlan(canvas["S"], canvas["Hc"], canvas["Wc"], canvas["stride"], n, 1).pairs, CANVAS_UNET_BATCH)
     with torch.no_grad():
-        pipe = G.Pipeline.from_model_dir(args.model, n, steps=args.steps, guidance=7.5)
+        pipe = G.Pipeline.from_model_dir(args.model, nb, steps=args.steps, guidance=7.5)
         base = G.load_base_text(args.model)
-        te, tokenizer = G.load_text_encoder(args.model, run, 2 * n, base=base)
+        te, tokenizer = G.load_text_encoder(args.model, run, 2 * nb, base=base)
         pipe.set_run(run)
         enc = None
         if edit is not None and edit["auto"] is not None:      # before the prompts are encoded: the maker runs the same text encoder
@@ -671,10 +744,13 @@ def main(argv=None):
             print(f"wrote {auto_mask_path(args)}: {A.describe(auto_mask, stats)}")
             del maker
         T = base.geo.max_pos
-        prompts = [args.prompt] * n if p2p is None else [args.prompt] * nseeds + [p2p["edit_prompt"]] * nseeds
-        ids = G.tokenize(tokenizer, [""] * n + prompts, T).to(pipe.dev)
-        states = te.forward(ids, pins=False).view(2, n * T, -1)
-        latents = None if invert is not None else torch.cat([G.seeded_latent(s, pipe.size) for s in seeds] * (n // nseeds)).to(pipe.dev)
+        prompts = [args.prompt] * nb if p2p is None else [args.prompt] * nseeds + [p2p["edit_prompt"]] * nseeds
+        ids = G.tokenize(tokenizer, [""] * nb + prompts, T).to(pipe.dev)
+        states = te.forward(ids, pins=False).view(2, nb * T, -1)
+        if canvas is not None:
+            latents = torch.cat([G.seeded_canvas_latent(s, canvas["Hc"], canvas["Wc"]) for s in seeds]).to(pipe.dev)
+        else:
+            latents = None if invert is not None else torch.cat([G.seeded_latent(s, pipe.size) for s in seeds] * (n // nseeds)).to(pipe.dev)
         recorder = None
         if words is not None:
             from textboost_amd.attn_maps import AttnMapRecorder
@@ -695,7 +771,10 @@ def main(argv=None):
             bctl = BlendControl(pipe.unet, blend["source"], blend["edit"], words=blend["words"], start=blend["start"],
                                 threshold=blend["threshold"], found=blend["found"])
             what += f", blend {blend['words']}"
-        if invert is not None:      # the photo is encoded once and inverted under --prompt; the source row is pinned to that trajectory
+        if canvas is not None:      # the MultiDiffusion canvas (textboost_amd/canvas.py): every refusal has happened on the host already
+            rgbx = pipe.canvas_images(states[1], states[0], latents, stride=canvas["stride"],
+                                      what=what + f", canvas {canvas['Wc'] * canvas['factor']} x {canvas['Hc'] * canvas['factor']}")
+        elif invert is not None:      # the photo is encoded once and inverted under --prompt; the source row is pinned to that trajectory
             import numpy as np
             from textboost_amd import edit as E
             enc = E.EditEncoder(args.model, pipe.size)

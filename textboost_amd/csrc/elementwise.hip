@@ -3,6 +3,7 @@
 // Reference call sites are cited per kernel (all in /root/reference/train_textboost.py unless noted).
 #include "common.h"
 #include "dpm_step.h"
+#include "image_byte.h"
 #include "../../include/textboost_hip.h"
 
 namespace {
@@ -617,13 +618,7 @@ __global__ __launch_bounds__(256) void vae_image_kernel(const float* __restrict_
 }
 
 // decoder output -> resident RGBX image (the format of tb_img_pack_rgb: R | G << 8 | B << 16, X = 0), one pixel per lane.  Per channel
-// uint8(rint(clamp(x / 2 + 0.5, 0, 1) * 255)): x / 2 is exact, so the fma rounds once like the two torch ops; the product with 255 is rounded on
-// its own before rint (half-way cases would flip otherwise); NaN -> 0.  VEC: ld == 4 and a 16-byte aligned base, one dwordx4 load per pixel.
-__device__ __forceinline__ uint32_t image_byte(float x) {
-  const float v = fmaf(x, 0.5f, 0.5f);
-  const float c = v > 0.f ? fminf(v, 1.f) : 0.f;   // NaN compares false
-  return (uint32_t)rintf(__fmul_rn(c, 255.f));
-}
+// `image_byte` (image_byte.h).  VEC: ld == 4 and a 16-byte aligned base, one dwordx4 load per pixel.
 template <bool VEC>
 __global__ __launch_bounds__(256) void vae_image_rgbx_kernel(const float* __restrict__ in, int64_t ld, uint32_t* __restrict__ out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over B * HW pixels

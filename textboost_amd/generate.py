@@ -8,6 +8,7 @@ eval_dreambooth.py (`load_pipeline` :175-215, `generate_from_pipeline` :218-267,
     Pipeline.set_unet_adapters([...])           -> attn2.to_k / to_v = W + sum w_i B_i A_i (one exact-fp32 GEMM, rounded once); [] = the base weights
     Pipeline.edit_images(cond, uncond, noise, z0, strength, ...)  -> `images` from an encoded photo, optionally inside a mask (edit.py)
     Pipeline.invert_edit_images(cond, uncond, z0, p2p, ...)       -> a photo inverted to noise and edited by its prompt
+    Pipeline.canvas_images(cond, uncond, latents, ...)            -> wide and tall images: a canvas of overlapping windows
     generate_instance(pipe, base, run, ...)     -> <outdir>/seed<s>/<instance>/<prompt>.png for every seed, 25 prompts each
 
 Device work: `HipTextEncoder.forward`, `HipSampler.denoise` (guided DPM-Solver++ steps on `HipUNet.forward`), `HipVAEDecoder.decode_rgbx`
@@ -130,6 +131,13 @@ def seeded_latent(seed: int, size: int) -> torch.Tensor:
     """the one latent of a seed: CPU, fp32 draw, rounded to fp16 (returned as fp32 [1, 4, size, size])"""
     g = torch.Generator().manual_seed(int(seed))
     return torch.randn(1, 4, size, size, generator=g, dtype=torch.float32).half().float()
+
+
+def seeded_canvas_latent(seed: int, Hc: int, Wc: int) -> torch.Tensor:
+    """`seeded_latent` for a canvas of Hc x Wc cells (canvas.py): the same generator, an fp32 draw of [1, 4, Hc, Wc] rounded to fp16.  At
+    Hc == Wc == size it is `seeded_latent(seed, size)` bit for bit."""
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.randn(1, 4, int(Hc), int(Wc), generator=g, dtype=torch.float32).half().float()
 
 
 # ------------------------------------------------------------------------------------------------ reader of a trained output directory
@@ -422,6 +430,28 @@ class Pipeline:
         if not bool(torch.isfinite(x).all()):
             raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
         return self.vae.decode_rgbx(x)
+
+    def canvas_images(self, cond, uncond, latents, stride=None, decode_stride=None, what: str = "") -> torch.Tensor:
+        """Wide and tall images (the MultiDiffusion canvas): latents fp32 [n, 4, Hc, Wc] on the device, Hc, Wc >= size, text states
+        as in `images` (one prompt for all) -> int32 RGBX [n, f Hc, f Wc] (resident; f = the VAE's factor).  `HipSampler.denoise_canvas` at
+        `stride` cells (default size // 4), the finite check of `images`, then the canvas is decoded as size x size latent tiles at
+        `decode_stride` cells (default 3 size / 4), B at a time, and `tb_tile_blend` feathers them over the f (size - decode_stride) pixels
+        two neighbours share.  A size x size canvas is one window and one tile: the bytes of `images`."""
+        from . import ops
+        from .canvas import CanvasPlan, blend_ramp
+        S = self.size
+        f = self.vae.H // self.vae.h
+        ds = max(1, (3 * S) // 4) if decode_stride is None else decode_stride
+        n, _, Hc, Wc = latents.shape
+        tiles_of = CanvasPlan(S, Hc, Wc, ds, n, self.B)       # (refusals before the denoising)
+        x = self.sampler.denoise_canvas(cond, uncond, latents, stride=stride)
+        if not bool(torch.isfinite(x).all()):
+            raise FloatingPointError(f"non-finite latents after {self.steps} steps: {what}")
+        tiles = torch.stack([x[img, :, oy:oy + S, ox:ox + S] for img in range(n) for oy, ox in tiles_of.windows()])
+        rows, _, _ = self.vae.decode_tiles(tiles)
+        rgbx = torch.empty(n, f * Hc, f * Wc, dtype=torch.int32, device=x.device)
+        ops.tile_blend(rows, tiles_of, f, blend_ramp(S, ds, f), rgbx=rgbx)
+        return rgbx
 
     def edit_images(self, cond, uncond, noise, z0, strength, latent_mask=None, pixel_mask=None, init_rgbx=None, maps=None,
                     what: str = "", regions=None, region_steps=None) -> torch.Tensor:

@@ -625,6 +625,49 @@ def dpm_step_local_blend(x, eps2, m_prev, x2, n_per_b, B, guidance, alpha_t, sig
             L.ptr(mask), hw)
 
 
+def _canvas_tables(plan, dev, scale=1):
+    """the table arguments of a canvas entry point (device y, host y, ny, device x, host x, nx) from a `canvas.CanvasPlan`; origins times `scale`
+    (the VAE's factor for tiles)"""
+    oy, ox, oyd, oxd = plan.tables(dev, scale)
+    return L.ptr(oyd), L.ptr(oy), plan.ny, L.ptr(oxd), L.ptr(ox), plan.nx
+
+
+def canvas_gather(x, x2, plan, chunk, xh=None):
+    """The UNet input of chunk `chunk` of a canvas (csrc/canvas.hip): x fp32 [n, 4, Hc, Wc] -> x2 16-bit
+    [2 Bu, 4, S, S], rows r and Bu + r = the crop of pair chunk * Bu + r (`canvas.CanvasPlan`); rows past the pair list repeat the last
+    pair.  xh: the 16-bit canvas `canvas_step` wrote, copied instead of converting x."""
+    n, Bu, S = plan.n_images, plan.unet_batch, plan.S
+    assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (n, 4, plan.Hc, plan.Wc)
+    assert x2.dtype == L.half_dtype() and x2.is_contiguous() and x2.numel() == 2 * Bu * 4 * S * S
+    assert xh is None or (xh.dtype == L.half_dtype() and xh.is_contiguous() and tuple(xh.shape) == tuple(x.shape))
+    _launch("tb_canvas_gather", L.ptr(x), L.ptr(xh), L.ptr(x2), n, plan.Hc, plan.Wc, S, *_canvas_tables(plan, x.device), Bu, chunk)
+
+
+def canvas_step(x, eps_all, m_prev, plan, guidance, alpha_t, sigma_t, ca, cb, cc, xh=None):
+    """One guided DPM-Solver++(2M) step of a whole canvas (csrc/canvas.hip): eps_all 16-bit [n_chunks, 2 Bu, 4, S, S] (every chunk's UNet
+    output) is averaged over the windows that cover a cell, then `dpm_step`'s update runs on x / m_prev fp32 [n, 4, Hc, Wc].  xh (optional):
+    16-bit canvas = `dpm_step`'s conversion of the new x, the next `canvas_gather`'s source."""
+    n, Bu, S = plan.n_images, plan.unet_batch, plan.S
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, 4, plan.Hc, plan.Wc) for t in (x, m_prev))
+    assert eps_all.dtype == L.half_dtype() and eps_all.is_contiguous() and eps_all.numel() == plan.n_chunks * 2 * Bu * 4 * S * S
+    assert xh is None or (xh.dtype == L.half_dtype() and xh.is_contiguous() and tuple(xh.shape) == tuple(x.shape))
+    _launch("tb_canvas_step", L.ptr(x), L.ptr(eps_all), L.ptr(m_prev), L.ptr(xh), n, plan.Hc, plan.Wc, S,
+            *_canvas_tables(plan, x.device), Bu, guidance, alpha_t, sigma_t, ca, cb, cc)
+
+
+def tile_blend(tiles, plan, factor, ramp, image=None, rgbx=None):
+    """Decoded VAE tiles -> one image per canvas (csrc/canvas.hip): tiles fp32 [n * ntiles * P * P, ld >= 3] (P = factor * S; the rows the
+    decoder leaves in front of `vae_image`), tile origins = `plan`'s tables times `factor`, feathered over `ramp` pixels.  image fp32
+    [n, 3, Hp, Wp] in [0, 1] and / or rgbx int32 [n, Hp, Wp] (the resident format)."""
+    n, P, Hp, Wp = plan.n_images, factor * plan.S, factor * plan.Hc, factor * plan.Wc
+    assert tiles.dtype == torch.float32 and tiles.dim() == 2 and tiles.stride(1) == 1 and tiles.shape[0] >= plan.pairs * P * P
+    assert image is not None or rgbx is not None
+    assert image is None or (image.dtype == torch.float32 and image.is_contiguous() and tuple(image.shape) == (n, 3, Hp, Wp))
+    assert rgbx is None or (rgbx.dtype == torch.int32 and rgbx.is_contiguous() and tuple(rgbx.shape) == (n, Hp, Wp))
+    _launch("tb_tile_blend", L.ptr(tiles), tiles.stride(0), L.ptr(image), L.ptr(rgbx), n, Hp, Wp, P,
+            *_canvas_tables(plan, tiles.device, factor), ramp)
+
+
 def img_paste(gen, orig, mask, out=None):
     """mask ? gen : orig per pixel: gen / orig int32 RGBX [H, W] (rows may be strided), mask uint8 [H, W] (non-zero = gen) -> int32 [H, W]"""
     h, w = gen.shape

@@ -15,6 +15,10 @@ update and the per-step select of the kept cells are one launch as well (`tb_dpm
 `HipSampler.invert` walks an encoded photo UP the schedule (DDIM inversion, one `tb_invert_step` per level) and returns the trajectory;
 `denoise(p2p=..., pin=trajectory)` then keeps the source rows of a prompt-to-prompt edit on it (`tb_dpm_step_pin`), so the source image is
 the photo and the edited rows inherit its layout (inference.py --invert-image).
+
+`HipSampler.denoise_canvas` denoises a latent larger than the UNet's square as overlapping model-sized windows (MultiDiffusion): per step
+`tb_canvas_gather` and the UNet per chunk of windows, then one `tb_canvas_step` on the whole canvas (inference.py --width / --height,
+DESIGN.md 24).
 """
 from __future__ import annotations
 
@@ -295,6 +299,61 @@ class HipSampler:
         if ex_steps:
             self._excite_finish(excite)
         return self.x
+
+    # ------------------------------------------------------------------ MultiDiffusion canvas (canvas.py)
+    def denoise_canvas(self, cond_ehs, uncond_ehs, latents, stride=None, keep_trace=False):
+        """Wide and tall images: latents fp32 [n, 4, Hc, Wc] (Hc, Wc >= the UNet's S) are denoised as overlapping S x S windows at `stride`
+        cells (default S // 4), `canvas.CanvasPlan(S, Hc, Wc, stride, n, B)`: the image-window pairs run through the UNet B at a time, at the
+        batch 2B and the size it is built for.  cond / uncond: [B*77, D] as in `denoise`; all images and windows share the one prompt.
+        Per step and chunk: `tb_canvas_gather` (the chunk's crops -> x2; a ragged last chunk repeats its last pair), the UNet forward of
+        `denoise`, a copy of its output into eps_all; then ONE `tb_canvas_step`, which averages the windows' guided eps where they overlap
+        and takes the solver's step on the canvas, `m_prev` kept on the canvas (the update is linear, so this equals stepping every window
+        and averaging the results).  From the second step on the crops are copies of the step's own 16-bit canvas, which carries
+        `tb_dpm_step`'s conversion: at Hc == Wc == S the UNet sees what `denoise` shows it and the result has `denoise`'s bits.
+        No host synchronisation (capturable).  keep_trace: `self.canvas_trace` fp32 [steps+1, n, 4, Hc, Wc] = the canvas before step 0 and
+        after every step, `self.canvas_trace_h` the 16-bit canvases beside it (entry 0 unused: step 0 converts the fp32 canvas).
+        DPM-Solver++ only.  Returns the final canvas fp32 [n, 4, Hc, Wc] (a new tensor)."""
+        from .canvas import CanvasPlan
+        sch, unet = self.sch, self.unet
+        if not isinstance(sch, DPMSolverPP2M):
+            raise NotImplementedError(f"the canvas runs on the DPM-Solver++ scheduler only, not on {type(sch).__name__}")
+        if unet.H != unet.W:
+            raise ValueError(f"the canvas takes square windows; the UNet is built for {unet.H} x {unet.W}")
+        S = unet.H
+        if not torch.is_tensor(latents) or latents.dtype != torch.float32 or latents.dim() != 4 or latents.shape[1] != 4:
+            raise ValueError(f"latents {getattr(latents, 'dtype', type(latents).__name__)} {tuple(getattr(latents, 'shape', ()))}: expected "
+                             "float32 [n, 4, Hc, Wc]")
+        n, _, Hc, Wc = latents.shape
+        key = (Hc, Wc, max(1, S // 4) if stride is None else stride, n)
+        plans = self.__dict__.setdefault("_canvas_plans", {})
+        if key not in plans:      # kept with their device tables: a repeated call uploads nothing (graph capture)
+            plans[key] = CanvasPlan(S, Hc, Wc, key[2], n, self.B)       # (CanvasError: a ValueError)
+        plan = plans[key]
+        dev, half = self.x.device, L.half_dtype()
+        plan.tables(dev)
+        x = torch.empty(n, 4, Hc, Wc, device=dev)
+        m_prev = torch.zeros_like(x)
+        xh = torch.empty(n, 4, Hc, Wc, device=dev, dtype=half)
+        eps_all = torch.empty((plan.n_chunks,) + tuple(self.x2.shape), device=dev, dtype=half)
+        x.copy_(latents * sch.init_noise_sigma)
+        self.canvas_plan = plan
+        self.canvas_trace = self.canvas_trace_h = None
+        if keep_trace:
+            self.canvas_trace = torch.empty((self.steps + 1,) + tuple(x.shape), device=dev)
+            self.canvas_trace_h = torch.zeros((self.steps + 1,) + tuple(x.shape), device=dev, dtype=half)
+            self.canvas_trace[0].copy_(x)
+        ehs = torch.cat([uncond_ehs, cond_ehs]).to(half).contiguous()
+        for i in range(self.steps):
+            for c in range(plan.n_chunks):
+                ops.canvas_gather(x, self.x2, plan, c, xh=xh if i else None)
+                eps_all[c].copy_(unet.forward(self.x2, self.t_dev[i], ehs))
+            a_t, s_t = sch.data_prediction_scalars(i)
+            ca, cb, cc = sch.coefficients(i)
+            ops.canvas_step(x, eps_all, m_prev, plan, self.g, a_t, s_t, ca, cb, cc, xh=xh)
+            if keep_trace:
+                self.canvas_trace[i + 1].copy_(x)
+                self.canvas_trace_h[i + 1].copy_(xh)
+        return x
 
     # ------------------------------------------------------------------ prompt-to-prompt LocalBlend (local_blend.py, DESIGN.md 23)
     def _blend_start(self, blend, p2p, maps, regions, excite, pin):

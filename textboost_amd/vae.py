@@ -345,6 +345,23 @@ class HipVAEDecoder(HipVAEEncoder):
         ops.vae_image_rgbx(rgb, img, self.B, H * W)
         return img.view(self.B, H, W)
 
+    def decode_tiles(self, tiles):
+        """the decoder on any number of latent tiles, left unfinished: tiles fp32 [nt, 4, h, w] -> (fp32 NHWC rows [nt * H * W, 4] of
+        `_decode_rgb`, 3 columns used; H; W), for `ops.tile_blend` (the canvas).  The tiles run B at a time; each chunk's rows
+        are copied out because `_decode_rgb` reuses its buffer, and a short last chunk is filled with its last tile (every image has its own
+        GroupNorm and attention statistics, so the filling changes nothing)."""
+        B, nt = self.B, tiles.shape[0]
+        HW = self.H * self.W
+        out = torch.empty(nt * HW, 4, device=tiles.device, dtype=torch.float32)
+        for c0 in range(0, nt, B):
+            chunk = tiles[c0:c0 + B]
+            m = chunk.shape[0]
+            if m < B:
+                chunk = torch.cat([chunk, chunk[-1:].expand(B - m, -1, -1, -1)])
+            rgb, _, _ = self._decode_rgb(chunk.contiguous())
+            out[c0 * HW:(c0 + m) * HW].copy_(rgb[:m * HW])
+        return out, self.H, self.W
+
     def _decode_rgb(self, latents):
         """-> (fp32 NHWC rows [B*H*W, 4] of `vae.decode(latents / scaling_factor).sample`, 3 columns used; H; W)"""
         geo, B, H, W = self.geo, self.B, self.h, self.w
