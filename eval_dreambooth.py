@@ -17,7 +17,8 @@ sub-directories of `path`) the trained output directory `<path>/<instance>[/chec
 and 25 prompts x `--seeds` are sampled (25 steps, guidance 7.5, one latent per seed) into
 `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/<prompt>.png`.  --model names a LOCAL diffusers model directory (unet/,
 vae/, text_encoder/, tokenizer/, scheduler/); the reference's aliases (sd15, ...) name hub repositories and are refused.  The scores are then
-computed from the PNGs exactly as a --skip-gen run computes them.
+computed from the PNGs exactly as a --skip-gen run computes them.  --freeu [B1 B2 S1 S2] and --freeu-backbone scalar|structure sample the
+images with FreeU, as inference.py does, so that its effect on a subject can be scored; they are refused with --skip-gen.
 
 Images are read from `<outdir>/<basename(path)>[-<checkpoint>][_<desc>]/seed<s>/<instance>/*.png`; the scores go to
 `<path>/metric{_ckpt<N>|_last}{_<desc>}.csv` in the reference's format.  --clip-model names a local transformers
@@ -71,7 +72,24 @@ def build_parser():
     p.add_argument("--vqa-model", type=str, default=None,
                    help="local clip-flant5 directory (config.json, T5 + mm_projector weights, tokenizer files); its vision tower is --clip-model's")
     p.add_argument("--batch-size", type=int, default=32, help="images per tower launch")
+    from textboost_amd import freeu as F
+    F.add_arguments(p)      # (image generation only)
     return p
+
+
+def check_freeu_args(parser, args):
+    """--freeu / --freeu-backbone of the generation stage -> None or (b1, b2, s1, s2, mode); refused by flag name before any model is built"""
+    from textboost_amd import freeu as F
+    F.check_count(parser, args)
+    if args.skip_gen:
+        for flag, given in (("--freeu", args.freeu is not None), ("--freeu-backbone", args.freeu_backbone is not None)):
+            if given:
+                raise SystemExit(f"eval_dreambooth.py: {flag} shapes the images the generation stage samples; --skip-gen scores images that "
+                                 "exist already")
+    try:
+        return F.resolve(args.freeu, args.freeu_backbone, args.model)
+    except F.FreeUError as e:
+        raise SystemExit(f"eval_dreambooth.py: {e}")
 
 
 def check_args(args):
@@ -289,11 +307,13 @@ def generate(args):
     except SystemExit as e:
         raise SystemExit(f"eval_dreambooth.py: {e}") from None
     return generate_run(path, args.model, instances, args.seeds, image_root(args), checkpoint=args.checkpoint, token_format=args.token_format,
-                        prompt_batch=args.prompt_batch)
+                        prompt_batch=args.prompt_batch, freeu=getattr(args, "freeu_factors", None))
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    args.freeu_factors = check_freeu_args(parser, args)
     check_args(args)
     if not args.skip_gen:
         generate(args)

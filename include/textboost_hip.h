@@ -820,6 +820,21 @@ int tb_mask_from_score(const float* score, const float* minmax, const float* thr
  * 0 <= radius <= 64 (0 copies).  One pass: a 64 x 64 tile and its halo in LDS, rows then columns. */
 int tb_mask_dilate(const uint8_t* in, uint8_t* out, int W, int H, int radius, tb_stream_t stream);
 
+/* ---- FreeU (csrc/freeu.hip; inference.py --freeu, HipUNet.enable_freeu; Si et al., "FreeU: Free Lunch in Diffusion U-Net") ----
+ * In place on the concat input [hidden | skip] of one decoder resnet: x TB_F16 rows [B * H * W, ld >= hc + sc], NHWC, image i = rows
+ * [i H W, (i + 1) H W), hidden = columns [0, hc), skip = columns [hc, hc + sc).  Columns [hc / 2, hc) and [hc + sc, ld) are never written.
+ *   skip (s != 1):  y = x + (s - 1) / (H W) * sum over the frequencies (u, v) in {0, -1} x {0, -1} of (C_uv cos t_uv + S_uv sin t_uv),
+ *                   t_uv(h, w) = 2 pi (u h / H + v w / W), C_uv = sum x cos t_uv, S_uv = sum x sin t_uv per (image, channel): diffusers'
+ *                   fourier_filter(x, threshold = 1, scale = s) without the FFT (an axis of length 1 has the frequency 0 only)
+ *   hidden, TB_FREEU_SCALAR (b != 1):     x[:, : hc / 2] *= b
+ *   hidden, TB_FREEU_STRUCTURE (b != 1):  m[p] = mean over all hc channels at pixel p; per image n[p] = (m[p] - min m) / (max m - min m)
+ *                                         (0 when max m == min m); x[p, : hc / 2] *= (b - 1) n[p] + 1
+ * fp32 moments and statistics summed in a fixed order, every output rounded once, one owner per element, no atomics: a repeat is
+ * bit-identical.  b == 1 / s == 1 launch nothing for that half.  NULL x; B, H, W <= 0; hc <= 0, hc odd or sc <= 0; ld < hc + sc; b or s not
+ * finite; an unknown mode; B > 65535, H or W > 256, H * W > 4096, hc or sc > 2^20: TB_EINVAL, nothing launched. */
+enum { TB_FREEU_SCALAR = 0, TB_FREEU_STRUCTURE = 1 };
+int tb_freeu(void* x, int64_t ld, int B, int H, int W, int hc, int sc, float b, float s, int mode, tb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ textboost_amd/generate.py.
         [--excite WORD [WORD ...] [--excite-steps F] [--excite-scale S] [--excite-loss-scale V] [--no-excite-refine]]
         [--blend WORD [WORD ...] [--blend-start F] [--blend-threshold T]]
         [--width PX] [--height PX] [--window-stride CELLS]
+        [--freeu [B1 B2 S1 S2]] [--freeu-backbone scalar|structure]
 
 `<output_dir>` is read as eval_dreambooth.py reads it (text_encoder/ adapter, every `<token>.bin`) and, beyond the reference, with the UNet
 cross-attention K/V adapters of a `--unet_params_to_train crossattn_kv` run (`<output_dir>/unet/`) folded into the UNet; the text encoder is the plain CLIP text model
@@ -103,6 +104,15 @@ before.  Not with --init-image, --mask, --invert-image, --edit-prompt, --reweigh
 places things on the model's own grid.  The paper's stride is 8 cells; the default here is a cost choice and has not been measured on pretrained
 weights.
 
+--freeu [B1 B2 S1 S2] turns FreeU on (textboost_amd/freeu.py; Si et al. 2024): in the first two decoder stages the first half of
+the backbone channels is amplified (B1, B2) and the lowest spatial frequencies of the skip features are damped (S1, S2), one in-place kernel
+launch in front of each of their resnets.  Without values the constants of the FreeU authors' README apply, chosen by the UNet's
+cross_attention_dim (768, SD1.x: 1.5 1.6 0.9 0.2; 1024, SD2.x: 1.4 1.6 0.9 0.2; they have not been measured here); another model needs the
+four values.  --freeu-backbone structure scales by (B - 1) n + 1, n the image's min-max normalised channel mean, instead of by B.  Values are
+finite and > 0; `--freeu 1 1 1 1` is the plain image.  Give the flag behind `<output_dir>`.  It goes with every forward-only path above
+(an --invert-image inversion and the generation run the same FreeU model; a --mask auto:WORD mask is made by the plain model), not with
+--excite, which needs the UNet's backward: FreeU works in place and keeps nothing for one.
+
 Differences from the reference: --model is a local diffusers model directory (the reference's alias handling raises KeyError); --checkpoint N
 reads `<output_dir>/checkpoint-N` (the reference parses the flag and ignores it); --outdir and --skip-gen are accepted and unused, as there; the
 latent of a seed is drawn on the CPU (textboost_amd.generate.seeded_latent), the same on every machine."""
@@ -191,7 +201,21 @@ def build_parser():
     p.add_argument("--window-stride", dest="window_stride", type=int, default=None, metavar="CELLS",
                    help="with --width / --height: latent cells between neighbouring windows, 1 .. the model's latent side (default a quarter "
                         "of it, 16 at SD1.x, where the paper uses 8: a cost choice, not measured on pretrained weights here)")
+    from textboost_amd import freeu as F
+    F.add_arguments(p)
     return p
+
+
+def check_freeu_flags(args):
+    """--freeu / --freeu-backbone: every refusal, on the host, by flag name, before any model is built.  -> None or (b1, b2, s1, s2, mode)"""
+    from textboost_amd import freeu as F
+    if args.freeu is not None and args.excite:
+        raise SystemExit("inference.py: --freeu does not go with --excite: the excite pass needs the UNet's backward, and FreeU rewrites the "
+                         "decoder's concat inputs in place, so nothing is kept for one")
+    try:
+        return F.resolve(args.freeu, args.freeu_backbone, args.model)
+    except F.FreeUError as e:
+        raise SystemExit(f"inference.py: {e}")
 
 
 MAX_CANVAS_PX = 8192
@@ -689,11 +713,15 @@ def write_attn_maps(stem, images, word_maps, words, seeds):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    from textboost_amd import freeu as F
+    F.check_count(parser, args)      # (argparse's own refusal: usage and exit status 2)
     from textboost_amd import generate as G
     if not args.model:
         raise SystemExit("inference.py: --model DIR (a local diffusers model directory: unet/, vae/, text_encoder/, tokenizer/, scheduler/) is required")
     G.check_model_dir(args.model, "inference.py")
+    freeu = check_freeu_flags(args)
     canvas = check_canvas_flags(args)
     check_excite_flags(args)
     check_invert_flags(args)
@@ -743,6 +771,10 @@ def main(argv=None):
             edit["mask"].save(auto_mask_path(args))
             print(f"wrote {auto_mask_path(args)}: {A.describe(auto_mask, stats)}")
             del maker
+        if freeu is not None:      # behind the mask maker: an auto mask is the plain model's attention in the photo
+            from textboost_amd.freeu import describe
+            pipe.unet.enable_freeu(*freeu[:4], mode=freeu[4])
+            print(describe(freeu))
         T = base.geo.max_pos
         prompts = [args.prompt] * nb if p2p is None else [args.prompt] * nseeds + [p2p["edit_prompt"]] * nseeds
         ids = G.tokenize(tokenizer, [""] * nb + prompts, T).to(pipe.dev)

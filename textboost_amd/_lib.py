@@ -22,6 +22,7 @@ ACT_LN_FWD, ACT_LN_BWD = 8, 9
  ST_SUMSQ_LORA, ST_SUMSQ_EMB, ST_LOSS_MSE, ST_LOSS_KPL, ST_LR_MULT, ST_LOSS_ATTN) = range(15)
 ST_COUNT = 16
 A_LINEAR, A_CONV3X3 = 0, 1
+FREEU_SCALAR, FREEU_STRUCTURE = 0, 1
 
 # {entry point: ([argtypes], restype)} and the descriptor structs (ctypes.Structure classes), read from include/textboost_hip.h
 _STRUCTS, _SIGS = _abi.load()[:2]

@@ -564,8 +564,10 @@ def generate_instance(pipe: Pipeline, base: BaseText, run: TrainedRun, instance:
 
 
 def generate_run(path: str, model_dir: str, instances: Sequence[str], seeds: Sequence[int], image_root: str, checkpoint: Optional[int] = None,
-                 token_format: str = "<INSTANCE> SUBJECT", steps: int = 25, guidance: float = 7.5, prompt_batch: int = 16, device="cuda") -> dict:
-    """`generate` (:270-350) over the subjects: executors once, the text encoder per subject.  -> {"images", "seconds", ...}"""
+                 token_format: str = "<INSTANCE> SUBJECT", steps: int = 25, guidance: float = 7.5, prompt_batch: int = 16, device="cuda",
+                 freeu=None) -> dict:
+    """`generate` (:270-350) over the subjects: executors once, the text encoder per subject.  -> {"images", "seconds", ...}
+    freeu: None or (b1, b2, s1, s2, mode) of `freeu.resolve`: every image is sampled with FreeU (`HipUNet.enable_freeu`)."""
     if not torch.cuda.is_available():
         raise SystemExit("image generation needs an MI355X: the product path has no CPU fallback")
     from . import _lib
@@ -576,6 +578,8 @@ def generate_run(path: str, model_dir: str, instances: Sequence[str], seeds: Seq
     t0 = time.perf_counter()
     with torch.no_grad():
         pipe = Pipeline.from_model_dir(model_dir, n_batch, steps=steps, guidance=guidance, device=device)
+        if freeu is not None:
+            pipe.unet.enable_freeu(*freeu[:4], mode=freeu[4])
         base = load_base_text(model_dir, device)
         timings: dict = {}
         with ThreadPoolExecutor(max_workers=MAX_PNG_THREADS) as pool:

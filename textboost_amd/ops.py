@@ -668,6 +668,19 @@ def tile_blend(tiles, plan, factor, ramp, image=None, rgbx=None):
             *_canvas_tables(plan, tiles.device, factor), ramp)
 
 
+FREEU_MODES = {"scalar": L.FREEU_SCALAR, "structure": L.FREEU_STRUCTURE}
+
+
+def freeu(cat, B, H, W, hc, b, s, mode="scalar"):
+    """FreeU in place on the concat input `cat` 16-bit [B * H * W, hc + sc] of a decoder resnet (csrc/freeu.hip):
+    hidden = columns [0, hc), of which the first hc / 2 are amplified (`scalar`: by b; `structure`: by (b - 1) n + 1, n the image's
+    min-max normalised channel mean), skip = the other columns, whose frequencies {0, -1} x {0, -1} are scaled by s."""
+    if mode not in FREEU_MODES:
+        raise ValueError(f"FreeU backbone mode {mode!r}: one of {sorted(FREEU_MODES)}")
+    assert cat.dtype == L.half_dtype() and cat.dim() == 2 and cat.stride(1) == 1 and cat.shape[0] == B * H * W and cat.shape[1] > hc
+    _launch("tb_freeu", L.ptr(cat), cat.stride(0), B, H, W, hc, cat.shape[1] - hc, b, s, FREEU_MODES[mode])
+
+
 def img_paste(gen, orig, mask, out=None):
     """mask ? gen : orig per pixel: gen / orig int32 RGBX [H, W] (rows may be strided), mask uint8 [H, W] (non-zero = gen) -> int32 [H, W]"""
     h, w = gen.shape

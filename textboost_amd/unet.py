@@ -17,6 +17,7 @@ buffers, the layer schedule and the weight re-packing:
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
@@ -123,6 +124,7 @@ class HipUNet:
         self.attn_loss = None   # enable_attn_loss(): the cross-attention localisation loss in the backward of the supervised layers (None = no launch)
         self.excite = None      # enable_excite(): Attend-and-Excite -- forward(until="excite") / backward_sample() record and inject (None = no launch)
         self.blend = None       # enable_blend(): prompt-to-prompt LocalBlend -- a full forward records the conditional rows' level-2 maps (None = no launch)
+        self.freeu = None       # enable_freeu(): FreeU -- one in-place launch on the concat input of every resnet of up_blocks.0 / .1 (None = no launch)
         self._cut = None        # the layer a truncated forward (until="excite") stops behind; None in a normal forward
         self._bwd_through = False   # backward_sample(): the backward does not stop at the first cross-attention
         self._bufs: Dict[str, torch.Tensor] = {}
@@ -218,6 +220,28 @@ class HipUNet:
         ex = self.excite
         ops.excite_loss(ex.acc, ex.last, ex.words, ex.h, ex.w, loss_scale, ex.loss, ex.word, ex.sel, ex.dA, check=check)
         return ex.loss
+
+    # ------------------------------------------------------------------ FreeU
+    def enable_freeu(self, b1: float, b2: float, s1: float, s2: float, mode: str = "scalar"):
+        """--freeu: in front of every resnet of up_blocks.0 (b1, s1) and up_blocks.1 (b2, s2) one `ops.freeu` launch re-weights the concat
+        input in place: the first half of the hidden channels is amplified (`scalar`: by b; `structure`: by (b - 1) n + 1, n the min-max
+        normalised channel mean of the image) and the lowest frequencies of the skip channels are scaled by s.  The stage is the up block's
+        index, as in diffusers' `apply_freeu`.  In place: such a forward keeps nothing a backward could walk (`backward`, `backward_sample`
+        and `forward(until="excite")` refuse).  Nothing is allocated; a factor of 1 launches nothing for its half."""
+        if self.dtype == torch.float32:
+            raise NotImplementedError("FreeU has 16-bit kernels only (an fp32 UNet has no FreeU launch)")
+        if len(self.geo.block_out_channels) < 2:
+            raise ValueError("FreeU re-weights up_blocks.0 and up_blocks.1; this UNet has fewer than two up blocks")
+        if mode not in ops.FREEU_MODES:
+            raise ValueError(f"FreeU backbone mode {mode!r}: one of {sorted(ops.FREEU_MODES)}")
+        vals = tuple(float(v) for v in (b1, b2, s1, s2))
+        if not all(math.isfinite(v) and v > 0 for v in vals):
+            raise ValueError(f"FreeU factors (b1, b2, s1, s2) = {vals}: finite and > 0")
+        self.freeu = SimpleNamespace(b=(vals[0], vals[1]), s=(vals[2], vals[3]), mode=mode)
+        return self.freeu
+
+    def disable_freeu(self):
+        self.freeu = None
 
     # ------------------------------------------------------------------ prompt-to-prompt LocalBlend (DESIGN.md section 23)
     BLEND_LEVEL = 2   # the recorded maps: (H >> 2) x (W >> 2), as Attend-and-Excite's
@@ -762,6 +786,9 @@ class HipUNet:
         if until is not None:
             if until != "excite":
                 raise ValueError(f"until={until!r}: only \"excite\" is built")
+            if self.freeu is not None:
+                raise ValueError("forward(until=\"excite\") with FreeU enabled: FreeU rewrites the concat inputs in place, the tape the "
+                                 "Attend-and-Excite backward walks would not be the forward's")
             if self.excite is None:
                 raise RuntimeError("forward(until=\"excite\") needs enable_excite()")
             self.excite.record = True
@@ -875,6 +902,9 @@ class HipUNet:
                     dst = self.buf(f"up.{i}.out", Ms[lvl], c)
                 else:
                     dst = self.buf("up.final", Ms[lvl], c)
+                if self.freeu is not None and i < 2:
+                    # cb is complete here (no up-path resnet takes a deferred operand) and its skip half has no reader left but this resnet
+                    ops.freeu(cb, B, hw[lvl][0], hw[lvl][1], hc, self.freeu.b[i], self.freeu.s[i], self.freeu.mode)
                 if has_attn:
                     mid = self.buf(f"up.{i}.{j}.res", Ms[lvl], c)
                     rb, pk = self._resnet(f"up_blocks.{i}.resnets.{j}", cb, mid, hw[lvl], defer_out=True)
@@ -918,7 +948,7 @@ class HipUNet:
         pred = self.buf("pred", B * 4, self.H * self.W).view(B, 4, self.H, self.W)
         ops.conv_to4(a, P["conv_out.wp"], P["conv_out.b"], pred, B, self.H, self.W, ch[0])
         self._saved = dict(final=x, sto=sto, cats=cats, cat_views=cat_views, down=down_records, mid=mid_records, up=up_records,
-                           hw=hw, Ms=Ms, ehs16=ehs16)
+                           hw=hw, Ms=Ms, ehs16=ehs16, freeu=self.freeu is not None)
         # `ehs_ready` may carry compute (the trainer issues the whole text-encoder forward from it, TextBoostStep.te_fwd_late): a geometry
         # without any cross-attention layer never reached `_ensure_kv` above -- run it here so that the callback is guaranteed to have happened
         self._ensure_kv()
@@ -927,6 +957,8 @@ class HipUNet:
     # ------------------------------------------------------------------ backward (dgrad only, down to d_ehs)
     def backward(self, dpred, d_ehs_out=None):
         S, geo, B, P = self._saved, self.geo, self.B, self.P
+        if S.get("freeu"):
+            raise ValueError("backward after a FreeU forward: FreeU rewrote the concat inputs in place, nothing is kept for a backward")
         if self.attn_loss is not None:
             self.attn_loss.coef_done.clear()
         ch = geo.block_out_channels
@@ -1057,6 +1089,8 @@ class HipUNet:
         if self.dtype == torch.float32:
             raise NotImplementedError("backward_sample has 16-bit kernels only")
         S, geo, B, P = self._saved, self.geo, self.B, self.P
+        if S.get("freeu"):
+            raise ValueError("backward_sample after a FreeU forward: FreeU rewrote the concat inputs in place, nothing is kept for a backward")
         truncated = bool(S.get("truncated", False))
         inject = (dpred is None) if excite is None else bool(excite)
         if inject and self.excite is None:
